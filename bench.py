@@ -14,6 +14,11 @@ split the proposals and new particles.
 
     python bench.py [--gpus N --steps K --warmup W]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+``--dump-outputs DIR`` also writes what the last timed step returned
+(``DIR/<name>.npy``).  ``--full`` adds what takes runs of its own: the KDE
+roofline (the live issue probe) and the CPU baseline leg.
 """
 import argparse
 import json
@@ -319,6 +324,41 @@ def rank_slice_report(args, comm, N, d, S, ms_step, stages, kde_ms,
     }
 
 
+# --dump-outputs: per-particle arrays larger than this many rows are written
+# as a fixed, seeded row sample (2^19 rows of theta, distance and weight at
+# d = 8 are 42 MB)
+DUMP_MAX_ROWS = 1 << 19
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(path, theta, dist, w, n_eval, eps, fit):
+    """What the last timed step handed its caller, as ``path/<name>.npy``
+    (float64): the new population (theta, distances, normalised weights; the
+    same seeded row sample of each when it has more than DUMP_MAX_ROWS rows,
+    ``rows.npy`` holding the row numbers), the evaluation count, the next
+    epsilon and the next transition's covariance."""
+    os.makedirs(path, exist_ok=True)
+    n = theta.shape[0]
+    if n > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(
+            n, DUMP_MAX_ROWS, replace=False))
+    else:
+        rows = np.arange(n)
+    sel = torch.as_tensor(rows, device=theta.device)
+    arrays = {
+        "rows": rows,
+        "theta": theta.index_select(0, sel).cpu().numpy(),
+        "distance": dist.index_select(0, sel).cpu().numpy(),
+        "weight": w.index_select(0, sel).cpu().numpy(),
+        "n_eval": np.array([int(n_eval)]),
+        "eps": np.array([eps]),
+        "cov": np.asarray(fit.cov),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"),
+                np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -330,6 +370,14 @@ def main():
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline "
+                         "figure does not need: the KDE roofline (live "
+                         "issue probe) and, on one GPU, the CPU baseline "
+                         "leg (--cpu-seconds, --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the new "
+                         "population, epsilon, covariance) as DIR/<name>.npy")
     ap.add_argument("--rank-slice", type=int, default=0, metavar="R",
                     help="one GPU runs rank 0's share of an R-GPU job "
                          "(pyabc_amd.distributed.RankSliceComm): B/R "
@@ -376,8 +424,12 @@ def main():
     K_ = args.steps
     pick = sorted({round(i * (K_ - 1) / 3) for i in range(4)}) if K_ > 4 \
         else list(range(K_))
+    cpu_leg = args.full and R == 1 and not args.no_cpu_baseline \
+        and not args.rank_slice
+    if not cpu_leg:
+        pick = []           # a plain run keeps no generation
     state = {"fit": fit, "eps": eps, "n_eval": 0, "t": 1, "sched": {},
-             "k": None}
+             "k": None, "last": None}
 
     stages = []     # --rank-slice: synchronised stage times per step
     sync_marks = {"on": False}
@@ -416,6 +468,7 @@ def main():
             tm.update({f"engine_{k}": v * 1e3 for k, v in eng.timers.items()})
             stages.append(tm)
         state["n_eval"] = n_eval
+        state["last"] = (th, dd, ww)
         state["t"] = t + 1
         return res
 
@@ -449,7 +502,6 @@ def main():
     ms_step = elapsed / args.steps * 1e3
     value = N * args.steps / elapsed
     flops_per_pair = 3 * d + 4
-    traffic, traffic_src = kde_traffic()
     # per-launch roofline of the dominant kernel on this rank
     avg_launch_s = kde_t / max(len(kde_ms), 1)
     pairs_per_launch = pairs_local / max(len(kde_ms), 1)
@@ -459,6 +511,11 @@ def main():
         f"ms/step={ms_step:.1f} kde avg launch {avg_launch_s*1e3:.1f} ms "
         f"({achieved_tf:.1f} TF/s) eps={state['eps']:.4g} "
         f"n_eval={state['n_eval']} phases={phases[-1]}")
+
+    if args.dump_outputs and comm.rank == 0:
+        # every rank holds the whole new population (all-gathered)
+        dump_outputs(args.dump_outputs, *state["last"], state["n_eval"],
+                     state["eps"], state["fit"])
 
     if args.rank_slice:
         # the stage breakdown: as many steps again, synchronised after each
@@ -498,11 +555,13 @@ def main():
             "parallelism": f"dp{R} (proposals + new particles sharded, "
                            f"population all-gathered per generation)"},
         "kde_pairs_per_s": pairs_total / kde_t_max,
-        "roofline": kde_roofline(d, achieved_tf, traffic, traffic_src,
-                                 avg_launch_s, pairs_per_launch,
-                                 tiles_per_launch),
     }
-    if R == 1 and not args.no_cpu_baseline:
+    if args.full:
+        traffic, traffic_src = kde_traffic()
+        out["roofline"] = kde_roofline(d, achieved_tf, traffic, traffic_src,
+                                       avg_launch_s, pairs_per_launch,
+                                       tiles_per_launch)
+    if cpu_leg:
         # the timed generations themselves, up to 4 evenly spaced ones
         sched = state["sched"]
         gens = [(sched[i][0].X.cpu().numpy(), sched[i][0].w.cpu().numpy(),

@@ -284,17 +284,21 @@ def test_rccl_collectives_one_rank_equal_no_comm():
 
 
 @pytest.mark.timeout(300)
-def test_bench_rccl_one_rank():
+def test_bench_rccl_one_rank(tmp_path):
     """bench.py under torchrun over RCCL ("nccl" backend), one rank with its
     collectives forced on: barrier, all-gathers and the max-over-ranks
-    timing run through RCCL and rank 0 prints one line."""
+    timing run through RCCL and rank 0 prints one line.  A plain run (no
+    --full): the line holds the headline figures and neither the roofline
+    nor the CPU baseline, and --dump-outputs writes the last step's
+    population."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
+    dump = tmp_path / "dump"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "1", "--steps", "1", "--warmup", "1", "--particles",
-           "40000", "--no-cpu-baseline"]
+           "40000", "--dump-outputs", str(dump)]
     env = dict(os.environ, ABC_COMM_FORCE="1")
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=280,
                        cwd=ROOT, env=env)
@@ -302,7 +306,19 @@ def test_bench_rccl_one_rank():
     lines = [json.loads(ln) for ln in p.stdout.splitlines()
              if ln.startswith("{")]
     assert len(lines) == 1, p.stdout
-    assert lines[0]["n_gpus"] == 1 and lines[0]["value"] > 0
+    r = lines[0]
+    assert r["n_gpus"] == 1 and r["value"] > 0 and r["steps"] == 1
+    assert r["ms_per_step"] > 0
+    assert "roofline" not in r and "cpu_baseline" not in r
+    got = {f[:-4]: np.load(dump / f) for f in os.listdir(dump)}
+    assert sorted(got) == ["cov", "distance", "eps", "n_eval", "rows",
+                           "theta", "weight"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["theta"].shape == (40000, 8) and got["cov"].shape == (8, 8)
+    assert got["distance"].shape == got["weight"].shape == (40000,)
+    assert np.isfinite(got["theta"]).all() and got["eps"][0] > 0
+    assert got["weight"].sum() == pytest.approx(1.0, abs=1e-12)
+    assert got["n_eval"][0] >= 40000
 
 
 @pytest.mark.timeout(300)
@@ -316,7 +332,7 @@ def test_bench_two_rank_rehearsal():
            "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "1", "--warmup", "1", "--particles", "40000",
-           "--rehearse-gloo", "--no-cpu-baseline"]
+           "--rehearse-gloo", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=280,
                        cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]

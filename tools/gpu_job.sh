@@ -11,7 +11,8 @@
 #   suite                 the whole -m gpu suite (+ the parity json files)
 #   tests=EXPR[@FILES]    pytest -m gpu -k EXPR [FILES, comma-separated]
 #   smoke                 __graft_entry__.smoke()
-#   bench[=ARGS]          bench.py (default --steps 20 --warmup 5)
+#   bench[=ARGS]          bench.py (default --full --steps 20 --warmup 5:
+#                         the roofline and the CPU baseline leg included)
 #   rankslice             bench.py --rank-slice R for R = 1, 2, 4, 8
 #   profile=TAG           rocprofv3 kernel stats + PMC passes of the bench
 #                         (one counter group per pass) -> prof_TAG/
@@ -61,7 +62,8 @@ for step in "$@"; do
         "import __graft_entry__ as g; g.smoke()" ;;
     bench)
       # shellcheck disable=SC2086
-      run 400 "${k}_bench" python3 -u bench.py ${arg:---steps 20 --warmup 5} ;;
+      run 400 "${k}_bench" python3 -u bench.py \
+        ${arg:---full --steps 20 --warmup 5} ;;
     rankslice)
       for R in 1 2 4 8; do
         run 300 "${k}_rankslice_$R" python3 -u bench.py --rank-slice $R \
