@@ -350,8 +350,13 @@ int abc_wquantile_exchange(int step, int64_t* offset_bytes, int64_t* count,
 /* ---------------- (a8) LocalTransition -----------------------------------
  * Replaces cKDTree(X).query(X, k+1)                 local_transition.py:82-83
  * _cov_and_inv / _cov per particle                  local_transition.py:112-139
- * and _pdf_single                                   local_transition.py:103-110 */
+ * and _pdf_single                                   local_transition.py:103-110
+ * Every entry point serves d <= 16 (the proposals d <= 16 / 32), except the
+ * fp32 pair loop abc_local_logpdf_f32 (d <= 8).  At d > 8 the kNN and the
+ * fp64 density need the larger workspaces of the _d queries below; at d <= 8
+ * the _d queries return the values of the queries without d. */
 size_t abc_knn_workspace_bytes(int64_t N, int k);
+size_t abc_knn_workspace_bytes_d(int64_t N, int d, int k);
 int abc_knn_f64(const double* X, int64_t N, int d, int k, int32_t* nbr,
                 double* nbr_d2, void* ws, size_t ws_bytes, hipStream_t stream);
 int abc_local_cov_f64(const double* X, const double* w, int64_t N, int d,
@@ -388,8 +393,10 @@ int abc_local_logpdf_f64(const double* pts, int64_t M, const double* X,
                          double* out_logpdf, void* ws, size_t ws_bytes,
                          hipStream_t stream);
 size_t abc_local_logpdf_workspace_bytes(int64_t M, int64_t N);
+size_t abc_local_logpdf_workspace_bytes_d(int64_t M, int64_t N, int d);
 /* the same density with the pair loop in fp32 (1e-5 relative; rows whose
- * sum falls below 2^-60 are re-evaluated exactly in fp64) */
+ * sum falls below 2^-60 are re-evaluated exactly in fp64).  d <= 8 only: at
+ * d = 9..16 abc_local_logpdf_mfma is the 1e-5 path. */
 int abc_local_logpdf_f32(const double* pts, int64_t M, const double* X,
                          const double* w, const double* inv_covs,
                          const double* dets, int64_t N, int d,
@@ -398,7 +405,11 @@ int abc_local_logpdf_f32(const double* pts, int64_t M, const double* X,
 size_t abc_local_logpdf_f32_workspace_bytes(int64_t M, int64_t N);
 /* the same density on the f16 matrix cores ("z form": q = |L^T (theta - X_n)|^2
  * with inv_n = L L^T, the GEMM on exact-grid f16 pieces, local_mfma.hip;
- * rows whose sum falls below 2^-32 are re-evaluated exactly in fp64) */
+ * rows whose sum falls below 2^-32 are re-evaluated exactly in fp64).
+ * d = 9..16: one particle per lane half, local_mfma16.hip; the workspace
+ * query returns the size of that form there.  After this call and after
+ * abc_local_logpdf_f64 the int32 at byte 16 of ws holds the number of rows
+ * that took the exact per-row fixup (read it on the call's stream). */
 int abc_local_logpdf_mfma(const double* pts, int64_t M, const double* X,
                           const double* w, const double* inv_covs,
                           const double* dets, int64_t N, int d,

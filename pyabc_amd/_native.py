@@ -164,6 +164,7 @@ _SIGS = {
     "abc_wquantile_exchange": (c_int, [c_int, c_ptr, c_ptr, c_ptr]),
     # (a8)
     "abc_knn_workspace_bytes": (c_size, [c_i64, c_int]),
+    "abc_knn_workspace_bytes_d": (c_size, [c_i64, c_int, c_int]),
     "abc_knn_f64": (c_int, [c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr,
                             c_size, c_ptr]),
     "abc_local_cov_f64": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_int,
@@ -174,6 +175,7 @@ _SIGS = {
                                        c_int, c_i64, c_i64, c_dbl, c_ptr,
                                        c_ptr, c_ptr, c_ptr]),
     "abc_local_logpdf_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "abc_local_logpdf_workspace_bytes_d": (c_size, [c_i64, c_i64, c_int]),
     "abc_local_logpdf_f64": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr,
                                      c_ptr, c_i64, c_int, c_ptr, c_ptr,
                                      c_size, c_ptr]),

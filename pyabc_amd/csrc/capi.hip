@@ -53,7 +53,7 @@ int abc_preload(void) {
   return abc::preload_propose() + abc::preload_kde() + abc::preload_kde_mfma() +
          abc::preload_distance() + abc::preload_select() + abc::preload_stochastic() +
          abc::preload_local() + abc::preload_local_pdf32() + abc::preload_local_mfma() +
-         abc::preload_sort();
+         abc::preload_local_mfma16() + abc::preload_sort();
 }
 int abc_version(void) { return 10000; }  // 0.1.0
 }

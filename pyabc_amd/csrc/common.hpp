@@ -109,6 +109,7 @@ int preload_local();
 int preload_local_pdf32();
 int preload_sort();
 int preload_local_mfma();
+int preload_local_mfma16();
 
 // ---- wave / block reductions (64-lane waves) -------------------------------
 template <typename T>

@@ -21,6 +21,7 @@
 #include "philox.hpp"
 #include "spatial.hpp"
 #include "local_common.hpp"
+#include "local_wide.hpp"
 
 namespace abc {
 
@@ -33,6 +34,14 @@ namespace abc {
 #endif
 constexpr int kKnnRows = 4;     // rows per wave (one wave per block; 8 before
                                 // round 5: 7.6 -> 6.1 ms, tools/knn_ab.py)
+// d = 9..16: two rows per wave.  The rows live twice in VGPRs (packed pairs
+// for the filter, scalars for the box test), 2 R d registers: at d = 16,
+// R = 4 that is 128 before the candidate, the kept set and the re-rank's
+// registers (register counts of both forms: DESIGN.md section 4)
+#ifndef ABC_KNN_ROWS_WIDE
+#define ABC_KNN_ROWS_WIDE 2
+#endif
+constexpr int kKnnRowsWide = ABC_KNN_ROWS_WIDE;
 constexpr int kMaxK = 192;      // k > 64: buffer of 256 = k kept + 64 appended
 
 // Separately rounded fp64 ops: hipcc contracts a*b+c into an FMA by default
@@ -802,6 +811,150 @@ void convert(const S* src, int64_t n, D* dst, hipStream_t st) {
                        dim3(256), 0, st, src, n, dst);
 }
 
+// ---- the fp64 density at d = 9..16 (local_wide.hpp) ------------------------
+namespace {
+
+constexpr int kPdfwBatch = 8;  // particles per LDS batch (9.6 KiB at d = 16)
+constexpr int kPdfwPts = 2;    // evaluation points per thread
+
+// Block (row block, chunk s), chunk minor as in local_pdf_kernel; thread t
+// owns row slots r0 + 256 p + t, p < kPdfwPts.  rows / count: null (slot r is
+// row r of M), or the list of the rows to evaluate and its length on the
+// device.  A row's arithmetic does not depend on its slot.
+template <int D>
+__global__ __launch_bounds__(256) void local_pdfw_kernel(
+    const double* __restrict__ pts, int64_t M, const double* __restrict__ X,
+    const double* __restrict__ coef, const double* __restrict__ lc,
+    const unsigned long long* __restrict__ lc_max_key, int64_t N, int split,
+    int64_t nchunk, const int* __restrict__ rows, const int* __restrict__ count,
+    double* __restrict__ part) {
+  constexpr int NC = D * (D + 1) / 2, PB = kPdfwBatch, P = kPdfwPts;
+  constexpr int REC = D + NC + 1;
+  __shared__ double stage[PB * REC];
+  const int64_t nrows = count ? *count : M;
+  const int64_t b0 = static_cast<int64_t>(blockIdx.x / split) * (256 * P);
+  if (b0 >= nrows) return;  // block-uniform
+  const int s = blockIdx.x % split;
+  const double L = key_f64(*lc_max_key);
+  int64_t row[P];
+  double th[P][D], acc[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const int64_t r = b0 + 256 * p + threadIdx.x;
+    const int64_t rc = r < nrows ? r : nrows - 1;
+    row[p] = rows ? rows[rc] : rc;
+#pragma unroll
+    for (int q = 0; q < D; ++q) th[p][q] = pts[row[p] * D + q];
+    acc[p] = 0.0;
+  }
+  const int64_t n0 = static_cast<int64_t>(s) * nchunk;
+  int64_t n1 = n0 + nchunk;
+  if (n1 > N) n1 = N;
+  for (int64_t nb = n0; nb < n1; nb += PB) {
+    const int cnt = n1 - nb < PB ? static_cast<int>(n1 - nb) : PB;
+    __syncthreads();  // the previous batch is consumed
+    for (int e = threadIdx.x; e < cnt * REC; e += 256) {
+      const int64_t n = nb + e / REC;
+      const int o = e % REC;
+      stage[e] = o < D ? X[n * D + o]
+                       : (o < D + NC ? coef[n * NC + (o - D)] : lc[n] - L);
+    }
+    __syncthreads();
+    for (int j = 0; j < cnt; ++j) {
+      const double* __restrict__ rec = stage + j * REC;
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        double dl[D];
+#pragma unroll
+        for (int q = 0; q < D; ++q) dl[q] = th[p][q] - rec[q];
+        const double qf = local_qform<D>(dl, rec + D);
+        acc[p] += exp(fma(-0.5, qf, rec[D + NC]));
+      }
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < P; ++p)
+    if (b0 + 256 * p + threadIdx.x < nrows)
+      part[static_cast<int64_t>(s) * M + row[p]] = acc[p];
+}
+
+// local_pdf_final_kernel over the same rows; the rows whose fixed-offset sum
+// underflowed go to the list `under`
+__global__ __launch_bounds__(256) void local_pdfw_final_kernel(
+    const double* __restrict__ part, int64_t M, int split,
+    const unsigned long long* __restrict__ lc_max_key,
+    const double* __restrict__ logsumw, const int* __restrict__ rows,
+    const int* __restrict__ count, double* __restrict__ out,
+    int* __restrict__ n_under, int* __restrict__ under, double thresh) {
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (r >= (count ? *count : M)) return;
+  const int64_t i = rows ? rows[r] : r;
+  double S = 0.0;
+  for (int s = 0; s < split; ++s) S += part[s * M + i];
+  if (S >= thresh) {
+    out[i] = key_f64(*lc_max_key) + log(S) - *logsumw;
+  } else {  // exact two-pass evaluation
+    under[atomicAdd(n_under, 1)] = static_cast<int>(i);
+    out[i] = -INFINITY;
+  }
+}
+
+// the packed coefficients when the list holds a row
+__global__ __launch_bounds__(256) void local_coefw_kernel(
+    const double* __restrict__ invs, int64_t N, int d, double* __restrict__ coef,
+    const int* __restrict__ count) {
+  if (*count == 0) return;
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (n < N) local_pack_coef(invs, n, d, coef);
+}
+
+template <int D>
+void local_pdfw_launch(const double* pts, int64_t M, const double* X, int64_t N,
+                       const LocalWsWide& v, const int* rows, const int* count,
+                       int* under, int* n_under, double* out, unsigned fix_grid,
+                       hipStream_t st) {
+  const unsigned grid =
+      static_cast<unsigned>(ceil_div(M, 256 * kPdfwPts) * v.split);
+  hipLaunchKernelGGL((local_pdfw_kernel<D>), dim3(grid), dim3(256), 0, st, pts, M, X,
+                     v.coef, v.lc, v.lc_max_key, N, v.split, v.nchunk, rows, count,
+                     v.part);
+  hipLaunchKernelGGL(local_pdfw_final_kernel, dim3(ceil_div(M, 256)), dim3(256), 0, st,
+                     v.part, M, v.split, v.lc_max_key, v.logsumw, rows, count, out,
+                     n_under, under, 1e-280);
+  hipLaunchKernelGGL((local_pdf_fixup_kernel<D>), dim3(fix_grid), dim3(256), 0, st, pts,
+                     X, v.coef, v.lc, N, v.logsumw, n_under, under, out);
+}
+
+}  // namespace
+
+int local_wide_prepare(const double* w, const double* dets, const double* invs,
+                       int64_t N, int d, const LocalWsWide& v, bool with_coef,
+                       hipStream_t st) {
+  ABC_HIP(hipMemsetAsync(v.lc_max_key, 0, 16, st));  // the key, n_fix, n_under
+  local_sumw(w, N, v.split, v.part, v.logsumw, st);
+  hipLaunchKernelGGL(local_const_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, st, w,
+                     dets, invs, N, d, v.lc, with_coef ? v.coef : nullptr, v.lc_max_key);
+  return kOk;
+}
+
+void local_wide_pass(const double* pts, int64_t M, const double* X,
+                     const double* invs, int64_t N, int d, const LocalWsWide& v,
+                     const int* rows, const int* count, int* under, int* n_under,
+                     double* out, unsigned fix_grid, hipStream_t st) {
+  if (count)
+    hipLaunchKernelGGL(local_coefw_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, st,
+                       invs, N, d, v.coef, count);
+  switch (d) {
+#define L(DD)                                                                     \
+  case DD:                                                                        \
+    local_pdfw_launch<DD>(pts, M, X, N, v, rows, count, under, n_under, out,      \
+                          fix_grid, st);                                          \
+    break;
+    L(9) L(10) L(11) L(12) L(13) L(14) L(15) L(16)
+#undef L
+  }
+}
+
 }  // namespace abc
 
 using namespace abc;
@@ -837,6 +990,18 @@ int abc_propose_local_philox_f64(const double* X, int64_t N, int d,
   return kOk;
 }
 
+size_t abc_knn_workspace_bytes(int64_t N, int k);
+// d > 8: the coordinate blocks are [T*64][d] and the spatial index holds 16
+// dimensions (spatial.hpp); d <= 8: abc_knn_workspace_bytes(N, k)
+size_t abc_knn_workspace_bytes_d(int64_t N, int d, int k) {
+  if (d <= 8) return abc_knn_workspace_bytes(N, k);
+  if (N < 1) N = 1;
+  const int64_t T = ceil_div(N, kTile);
+  return 256 + al256(static_cast<size_t>(N) * 4) +
+         al256(static_cast<size_t>(T) * kTile * d * 4) +
+         al256(static_cast<size_t>(T) * kTile * d * 8) + spatial_ws_bytes(N, 16);
+}
+
 size_t abc_knn_workspace_bytes(int64_t N, int k) {
   (void)k;
   // amax | rows[N] | fp32 sorted centred coordinates [T*64][8] | fp64
@@ -858,8 +1023,10 @@ int abc_knn_rows_f64(const double* X, int64_t N, int d, int k, int64_t row0,
               (long long)(row0 + nrows), (long long)N);
   if (nrows == 0) return kOk;
   ABC_REQUIRE(X && nbr && ws, "knn: null pointer");
-  ABC_REQUIRE(ws_bytes >= abc_knn_workspace_bytes(N, k), "knn: workspace too small");
-  ABC_REQUIRE(d >= 1 && d <= 8, "knn: unsupported d=%d (d <= 8)", d);
+  ABC_REQUIRE(d >= 1 && d <= 16, "knn: unsupported d=%d (d <= 16)", d);
+  ABC_REQUIRE(ws_bytes >= abc_knn_workspace_bytes_d(N, d, k),
+              "knn: workspace too small (abc_knn_workspace_bytes_d for d > 8)");
+  const int cs = d <= 8 ? 8 : d;  // row stride the coordinate blocks are sized for
   char* q = static_cast<char*>(ws);
   unsigned long long* amax = reinterpret_cast<unsigned long long*>(q);
   q += 256;
@@ -867,10 +1034,10 @@ int abc_knn_rows_f64(const double* X, int64_t N, int d, int k, int64_t row0,
   q += al256(static_cast<size_t>(N) * 4);
   const int64_t T = ceil_div(N, kTile);
   float* Xs = reinterpret_cast<float*>(q);
-  q += al256(static_cast<size_t>(T) * kTile * 8 * 4);
+  q += al256(static_cast<size_t>(T) * kTile * cs * 4);
   double* Xd = reinterpret_cast<double*>(q);
-  q += al256(static_cast<size_t>(T) * kTile * 8 * 8);
-  SpatialWs v = spatial_ws(q, N);
+  q += al256(static_cast<size_t>(T) * kTile * cs * 8);
+  SpatialWs v = spatial_ws(q, N, d <= 8 ? 8 : 16);
   ABC_HIP(hipMemsetAsync(amax, 0, 8, st));
   // rows per wave: kKnnRows, or 8 (tuning knob ABC_KNN_ROWS; the neighbour
   // sets, order and distances are the same; 2 and 16 measured slower)
@@ -885,7 +1052,10 @@ int abc_knn_rows_f64(const double* X, int64_t N, int d, int k, int64_t row0,
     if (rpw == 8) KNN_R(DD, H, 8);                                               \
     else KNN_R(DD, H, kKnnRows);                                                 \
   } while (0)
-#define L(DD)                                                                    \
+#define KNNW(DD, H) KNN_R(DD, H, kKnnRowsWide)  // d > 8: ABC_KNN_ROWS has no say
+#define L(DD) LK(DD, KNN)
+#define LW(DD) LK(DD, KNNW)
+#define LK(DD, KNN)                                                              \
   {                                                                              \
     const int rc = spatial_sort_population<DD>(X, N, v, st);                     \
     if (rc != kOk) return rc;                                                    \
@@ -904,8 +1074,19 @@ int abc_knn_rows_f64(const double* X, int64_t N, int d, int k, int64_t row0,
     case 6: L(6) break;
     case 7: L(7) break;
     case 8: L(8) break;
+    case 9: LW(9) break;
+    case 10: LW(10) break;
+    case 11: LW(11) break;
+    case 12: LW(12) break;
+    case 13: LW(13) break;
+    case 14: LW(14) break;
+    case 15: LW(15) break;
+    case 16: LW(16) break;
   }
 #undef L
+#undef LW
+#undef LK
+#undef KNNW
 #undef KNN
   ABC_LAUNCH_CHECK("knn_kernel");
   return kOk;
@@ -973,6 +1154,12 @@ size_t abc_local_logpdf_workspace_bytes(int64_t M, int64_t N) {
          static_cast<size_t>(split) * M * 8 + static_cast<size_t>(M) * 4 + 512;
 }
 
+// d > 8: coef[N][d(d+1)/2]; d <= 8: abc_local_logpdf_workspace_bytes(M, N)
+size_t abc_local_logpdf_workspace_bytes_d(int64_t M, int64_t N, int d) {
+  if (d <= 8) return abc_local_logpdf_workspace_bytes(M, N);
+  return local_ws_wide_bytes(M > 0 ? M : 1, N > 0 ? N : 1, d);
+}
+
 int abc_local_logpdf_f64(const double* pts, int64_t M, const double* X,
                          const double* w, const double* inv_covs,
                          const double* dets, int64_t N, int d,
@@ -980,11 +1167,21 @@ int abc_local_logpdf_f64(const double* pts, int64_t M, const double* X,
                          hipStream_t st) {
   ABC_REQUIRE(M >= 0 && N >= 1, "local_logpdf: bad sizes");
   if (M == 0) return kOk;
-  ABC_REQUIRE(d >= 1 && d <= 8, "local_logpdf: unsupported d=%d (d <= 8)", d);
+  ABC_REQUIRE(d >= 1 && d <= 16, "local_logpdf: unsupported d=%d (d <= 16)", d);
   ABC_REQUIRE(pts && X && w && inv_covs && dets && out_logpdf && ws,
               "local_logpdf: null pointer");
-  ABC_REQUIRE(ws_bytes >= abc_local_logpdf_workspace_bytes(M, N),
-              "local_logpdf: workspace too small");
+  ABC_REQUIRE(ws_bytes >= abc_local_logpdf_workspace_bytes_d(M, N, d),
+              "local_logpdf: workspace too small "
+              "(abc_local_logpdf_workspace_bytes_d for d > 8)");
+  if (d > 8) {  // local_wide.hpp
+    const LocalWsWide v = local_ws_wide(ws, M, N, d);
+    const int rc = local_wide_prepare(w, dets, inv_covs, N, d, v, true, st);
+    if (rc != kOk) return rc;
+    local_wide_pass(pts, M, X, inv_covs, N, d, v, nullptr, nullptr, v.fix_rows, v.n_fix,
+                    out_logpdf, 64, st);
+    ABC_LAUNCH_CHECK("local_logpdf kernels");
+    return kOk;
+  }
   int split;
   int64_t nchunk;
   local_plan(M, N, split, nchunk);
@@ -1026,7 +1223,7 @@ int abc_local_logpdf_f64(const double* pts, int64_t M, const double* X,
 
 size_t abc_knn_topk_f32_workspace_bytes(int64_t N, int d, int k) {
   return al256(static_cast<size_t>(N) * d * 8) +
-         al256(static_cast<size_t>(N) * k * 8) + abc_knn_workspace_bytes(N, k);
+         al256(static_cast<size_t>(N) * k * 8) + abc_knn_workspace_bytes_d(N, d, k);
 }
 
 int abc_knn_topk_f32(const float* X, int64_t N, int d, int k, int32_t* nbr,

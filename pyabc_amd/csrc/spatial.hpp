@@ -39,7 +39,10 @@ __host__ __device__ inline int morton_bits(int d) {
 namespace {  // kernels: internal linkage in every including unit
 
 // Quantisation frame: per dimension the extent of (x - X[0]) over the
-// population as ordered fp64 keys, min in [q], max in [8 + q].
+// population as ordered fp64 keys, min in [q], max in [kSpExtHi<D> + q]
+// (8 for d <= 8, the layout every d <= 8 workspace has; 16 above).
+template <int D>
+constexpr int kSpExtHi = D <= 8 ? 8 : 16;
 template <int D>
 __global__ __launch_bounds__(256) void sp_extent_kernel(
     const double* __restrict__ X, int64_t N,
@@ -84,7 +87,7 @@ __global__ __launch_bounds__(256) void sp_extent_kernel(
     if (c < D)
       atomicMin(ext + c, v);
     else
-      atomicMax(ext + 8 + (c - D), v);
+      atomicMax(ext + kSpExtHi<D> + (c - D), v);
   }
 }
 
@@ -103,7 +106,7 @@ __global__ __launch_bounds__(256) void sp_key_kernel(
   uint64_t c[D];
 #pragma unroll
   for (int q = 0; q < D; ++q) {
-    const double lo = key_f64(ext[q]), hi = key_f64(ext[8 + q]);
+    const double lo = key_f64(ext[q]), hi = key_f64(ext[kSpExtHi<D> + q]);
     const double span = hi - lo;
     double v = span > 0.0 ? (P[i * D + q] - X[q] - lo) * (cells / span) : 0.0;
     v = v > 0.0 ? (v < cells ? v : cells) : 0.0;  // NaN -> 0
@@ -178,9 +181,10 @@ __device__ inline float box_dist2(const float (&x)[D], const float* __restrict__
 inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 // Workspace of the spatial index (spatial.hpp) over n points padded to
 // whole tiles: header (ext keys, counters) | keys_in[n] | keys_out[n] |
-// vals_in[n] | perm[T*64] | tbox[T][2][8] | sort temp.
+// vals_in[n] | perm[T*64] | tbox[T][2][8] | sort temp.  dcap = 16 (d > 8):
+// a 512-byte header (ext[32], the counters behind it) and tbox[T][2][16].
 struct SpatialWs {
-  unsigned long long* ext;  // [16]: per-dim min keys, then max keys
+  unsigned long long* ext;  // [2 dcap]: per-dim min keys, then max keys
   int* count;
   uint64_t* keys_in;
   uint64_t* keys_out;
@@ -192,20 +196,20 @@ struct SpatialWs {
   int T;
 };
 
-inline size_t spatial_ws_bytes(int64_t n) {
+inline size_t spatial_ws_bytes(int64_t n, int dcap = 8) {
   const int64_t T = ceil_div(n > 0 ? n : 1, kTile);
-  return 256 + 2 * al256(static_cast<size_t>(n) * 8) + al256(static_cast<size_t>(n) * 4) +
-         al256(static_cast<size_t>(T) * kTile * 4) + al256(static_cast<size_t>(T) * 2 * 8 * 4) +
-         al256(sort_pairs_temp_bytes(n));
+  return 32 * dcap + 2 * al256(static_cast<size_t>(n) * 8) + al256(static_cast<size_t>(n) * 4) +
+         al256(static_cast<size_t>(T) * kTile * 4) +
+         al256(static_cast<size_t>(T) * 2 * dcap * 4) + al256(sort_pairs_temp_bytes(n));
 }
 
-inline SpatialWs spatial_ws(void* ws, int64_t n) {
+inline SpatialWs spatial_ws(void* ws, int64_t n, int dcap = 8) {
   SpatialWs v;
   char* q = static_cast<char*>(ws);
   v.T = static_cast<int>(ceil_div(n > 0 ? n : 1, kTile));
   v.ext = reinterpret_cast<unsigned long long*>(q);
-  v.count = reinterpret_cast<int*>(q + 128);
-  q += 256;
+  v.count = reinterpret_cast<int*>(q + 16 * dcap);
+  q += 32 * dcap;
   v.keys_in = reinterpret_cast<uint64_t*>(q);
   q += al256(static_cast<size_t>(n) * 8);
   v.keys_out = reinterpret_cast<uint64_t*>(q);
@@ -215,7 +219,7 @@ inline SpatialWs spatial_ws(void* ws, int64_t n) {
   v.perm = reinterpret_cast<int32_t*>(q);
   q += al256(static_cast<size_t>(v.T) * kTile * 4);
   v.tbox = reinterpret_cast<float*>(q);
-  q += al256(static_cast<size_t>(v.T) * 2 * 8 * 4);
+  q += al256(static_cast<size_t>(v.T) * 2 * dcap * 4);
   v.temp = q;
   v.temp_bytes = al256(sort_pairs_temp_bytes(n));
   return v;
@@ -226,8 +230,9 @@ inline SpatialWs spatial_ws(void* ws, int64_t n) {
 template <int D>
 int spatial_sort_population(const double* X, int64_t N, SpatialWs& v,
                                    hipStream_t st) {
-  ABC_HIP(hipMemsetAsync(v.ext, 0xff, 64, st));
-  ABC_HIP(hipMemsetAsync(v.ext + 8, 0, 64 + 8, st));
+  constexpr int EH = kSpExtHi<D>;  // min keys, max keys, then the counter
+  ABC_HIP(hipMemsetAsync(v.ext, 0xff, 8 * EH, st));
+  ABC_HIP(hipMemsetAsync(v.ext + EH, 0, 8 * EH + 8, st));
   hipLaunchKernelGGL((sp_extent_kernel<D>), dim3(stream_grid(N, 256, 64)), dim3(256),
                      0, st, X, N, v.ext);
   hipLaunchKernelGGL((sp_key_kernel<D>), dim3(ceil_div(N, 256)), dim3(256), 0, st,

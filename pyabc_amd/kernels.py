@@ -592,12 +592,19 @@ def weighted_quantile(d, w, alpha, comm=None, shard=False):
 # ---------------------------------------------------------------------------
 # LocalTransition (a8)
 # ---------------------------------------------------------------------------
+def _knn_workspace_bytes(N, d, k):
+    # d > 8: coordinate blocks sized by d (abc_hip.h)
+    if d > 8:
+        return nat.lib().abc_knn_workspace_bytes_d(N, d, k)
+    return nat.lib().abc_knn_workspace_bytes(N, k)
+
+
 def knn(X, k):
     X = _contig(X, F64)
     N, d = X.shape
     nbr = torch.empty((N, k), dtype=torch.int32, device=_dev())
     d2 = torch.empty((N, k), dtype=F64, device=_dev())
-    wsb = nat.lib().abc_knn_workspace_bytes(N, k)
+    wsb = _knn_workspace_bytes(N, d, k)
     ws = WS.get(wsb, "knn")
     call("abc_knn_f64", ptr(X), N, d, k, ptr(nbr), ptr(d2), ptr(ws), wsb,
          nat.stream())
@@ -610,7 +617,7 @@ def knn_rows(X, k, row0, nrows):
     N, d = X.shape
     nbr = torch.empty((nrows, k), dtype=torch.int32, device=_dev())
     d2 = torch.empty((nrows, k), dtype=F64, device=_dev())
-    wsb = nat.lib().abc_knn_workspace_bytes(N, k)
+    wsb = _knn_workspace_bytes(N, d, k)
     ws = WS.get(wsb, "knn")
     call("abc_knn_rows_f64", ptr(X), N, d, k, row0, nrows, ptr(nbr), ptr(d2),
          ptr(ws), wsb, nat.stream())
@@ -644,18 +651,28 @@ def local_cov(X, w, nbr, scaling=1.0):
     return covs, invs, dets
 
 
-def local_logpdf(pts, X, w, invs, dets, precision="f64"):
+def local_logpdf(pts, X, w, invs, dets, precision="f64",
+                 return_fixups=False):
     """log LocalTransition density; ``precision`` "f64" (1e-12), "f32"
-    (pair loop in fp32, 1e-5 relative) or "mfma" (z form on the f16 matrix
-    cores, 1e-5 relative)."""
+    (pair loop in fp32, 1e-5 relative, d <= 8) or "mfma" (z form on the f16
+    matrix cores, 1e-5 relative, d <= 16).  ``return_fixups``: also return
+    the number of rows that took the exact per-row fixup ("f64", "mfma")."""
     if precision not in ("f64", "f32", "mfma"):
         raise ValueError(f"unknown LocalTransition precision {precision!r}")
     pts = _contig(pts, F64)
     M, d = pts.shape
     N = X.shape[0]
+    if precision == "f32" and d > 8:
+        raise ValueError(
+            f'LocalTransition precision "f32" serves d <= 8 (d={d}): use '
+            '"mfma" (1e-5 relative) or "f64"')
+    if return_fixups and precision == "f32":
+        raise ValueError('return_fixups needs precision "f64" or "mfma"')
     out = torch.empty(M, dtype=F64, device=_dev())
     if precision == "mfma":
         wsb = nat.lib().abc_local_logpdf_mfma_workspace_bytes(M, N, d)
+    elif d > 8:
+        wsb = nat.lib().abc_local_logpdf_workspace_bytes_d(M, N, d)
     else:
         wsb = getattr(nat.lib(), f"abc_local_logpdf{'_f32' if precision == 'f32' else ''}"
                       "_workspace_bytes")(M, N)
@@ -663,6 +680,9 @@ def local_logpdf(pts, X, w, invs, dets, precision="f64"):
     call(f"abc_local_logpdf_{precision}", ptr(pts), M, ptr(_contig(X, F64)),
          ptr(_contig(w, F64)), ptr(invs), ptr(dets), N, d, ptr(out), ptr(ws),
          wsb, nat.stream())
+    if return_fixups:
+        # the int32 at byte 16 of the workspace (abc_hip.h)
+        return out, int(ws[16:20].view(torch.int32).item())
     return out
 
 

@@ -227,7 +227,9 @@ class LocalTransition(Transition):
     """Local (k-nearest-neighbour covariance) Gaussian kernel on the GPU
     (local_transition.py:13-145): kNN by the one-pass device top-k, per
     particle weighted covariance + LU det/inverse, density by the device
-    quadratic-form pass."""
+    quadratic-form pass.  Up to 16 parameters; the fp32 pair loop
+    ``kde_precision="f32"`` serves up to 8 (above, "mfma" is the 1e-5 path
+    and the first density call with "f32" raises)."""
     EPS = 1e-3
     MIN_K = 10
 

@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT_LIB = os.path.join(ROOT, "pyabc_amd", "_lib", "libabc_hip.so")
 _MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 _FIELDS = (".sgpr_spill_count", ".vgpr_spill_count", ".private_segment_fixed_size",
-           ".vgpr_count", ".agpr_count", ".sgpr_count")
+           ".vgpr_count", ".agpr_count", ".sgpr_count", ".group_segment_fixed_size")
 
 
 def readelf():
@@ -59,16 +59,23 @@ def kernel_resources(lib=DEFAULT_LIB):
                 f.write(img)
             txt = subprocess.run([tool, "--notes", path], capture_output=True,
                                  text=True, check=True).stdout
-            # metadata keys are sorted: a kernel's .name precedes its counts
-            cur = None
+            # metadata keys are sorted: the counts that sort before .name
+            # (.agpr_count, .group_segment_fixed_size) precede their kernel's
+            # name, the others follow it
+            cur, early = None, {}
             for line in txt.splitlines():
                 s = line.strip()
+                if s.startswith("- "):
+                    s = s[2:]
                 if s.startswith(".name:"):
                     cur = s.split(None, 1)[1]
-                    res[cur] = {}
-                elif cur is not None and s.split(":")[0] in _FIELDS:
+                    res[cur], early = early, {}
+                elif s.split(":")[0] in _FIELDS:
                     key, val = s.split(":", 1)
-                    res[cur][key[1:]] = int(val)
+                    if key < ".name":
+                        early[key[1:]] = int(val)
+                    elif cur is not None:
+                        res[cur][key[1:]] = int(val)
     return res
 
 
