@@ -494,6 +494,25 @@ int abc_stochastic_kernel_f64(const double* stats_T, int64_t ld,
                               const double* u, uint64_t seed, uint64_t stream,
                               uint64_t offset, uint8_t* accept, double* accw,
                               uint8_t* guard, hipStream_t stream_);
+/* Full-covariance normal kernel on the fp64 matrix cores (stochastic_full.hip);
+ * replaces NormalKernel.__call__, distance/kernel.py:173-194
+ *     pd = multivariate_normal(cov).logpdf(x - x_0)
+ *   pd[b] = -0.5 * (c + sum_r (sum_s (stats_T[s ld + b] - x0[s]) U[s][r])^2)
+ * U [S][R] row-major is scipy's _PSD whitening factor and
+ * c = rank log(2 pi) + log_pdet (host: kernels.psd_whitening).  Not bit-equal
+ * to scipy (its BLAS dot has no fixed order): first-order rounding bound
+ * 0.5 (2S + R + 3) 2^-53 sum_r (sum_s |diff_s| |U_sr|)^2 + 2 2^-53 |pd|.
+ * pd[b] depends on column b, x0, U and c only (not on B, ld or b's place).
+ * The fused acceptance (accept != NULL), u, Philox and guard are those of
+ * abc_stochastic_kernel_f64.  1 <= S <= 4096, 1 <= R <= 4096, ld >= B;
+ * no workspace. */
+int abc_normal_kernel_f64(const double* stats_T, int64_t ld, const double* x0,
+                          const double* U /* [S][R] row-major */, int S, int R,
+                          double c, int64_t B, double* pd,
+                          double pdf_norm, double inv_temp, int apply_iw,
+                          const double* u, uint64_t seed, uint64_t stream,
+                          uint64_t offset, uint8_t* accept, double* accw,
+                          uint8_t* guard, hipStream_t stream_);
 /* StochasticAcceptor decision for given densities, SCALE_LOG (log_scale=1)
  * or SCALE_LIN: acc = (pd / pdf_norm) ** inv_temp.   acceptor/acceptor.py:456-473 */
 int abc_stochastic_accept_f64(const double* pd, int64_t B, double pdf_norm,

@@ -200,6 +200,10 @@ _SIGS = {
                                           c_int, c_dbl, c_i64, c_ptr, c_dbl,
                                           c_dbl, c_int, c_ptr, c_u64, c_u64,
                                           c_u64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "abc_normal_kernel_f64": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_int,
+                                      c_int, c_dbl, c_i64, c_ptr, c_dbl,
+                                      c_dbl, c_int, c_ptr, c_u64, c_u64,
+                                      c_u64, c_ptr, c_ptr, c_ptr, c_ptr]),
     "abc_stochastic_accept_f64": (c_int, [c_ptr, c_i64, c_dbl, c_dbl, c_int,
                                           c_int, c_ptr, c_u64, c_u64, c_u64,
                                           c_ptr, c_ptr, c_ptr, c_ptr]),

@@ -105,6 +105,7 @@ int preload_kde_mfma();
 int preload_distance();
 int preload_select();
 int preload_stochastic();
+int preload_stochastic_full();
 int preload_local();
 int preload_local_pdf32();
 int preload_sort();

@@ -361,7 +361,8 @@ class AdaptivePNormDistance(PNormDistance):
 # ---------------------------------------------------------------------------
 # stochastic kernels (distance/kernel.py:1-588): densities for the
 # StochasticAcceptor.  Independent normal / Laplace kernels evaluate through
-# abc_stochastic_kernel_f64 (single calls and the batch sampler alike).
+# abc_stochastic_kernel_f64 (single calls and the batch sampler alike); the
+# full-covariance NormalKernel's batches through abc_normal_kernel_f64.
 # ---------------------------------------------------------------------------
 SCALE_LIN = "SCALE_LIN"
 SCALE_LOG = "SCALE_LOG"
@@ -427,18 +428,23 @@ class SimpleFunctionKernel(StochasticKernel):
 
 class NormalKernel(StochasticKernel):
     """Multivariate normal density of x - x_0 (kernel.py:110-187), scipy's
-    ``multivariate_normal`` semantics (host; d x d parameters)."""
+    ``multivariate_normal`` semantics.  Single calls evaluate on the host
+    (d x d parameters); batches of SCALE_LOG densities on the device, as
+    -0.5 (rank log(2 pi) + log_pdet + |diff U|^2) with scipy's _PSD whitening
+    factor U (``kernels.psd_whitening``)."""
 
     def __init__(self, cov=None, ret_scale=SCALE_LOG, keys=None,
                  pdf_max=None):
         super().__init__(ret_scale=ret_scale, keys=keys, pdf_max=pdf_max)
         self.cov = cov
+        self._dev_cache = None
 
     def initialize(self, t, get_all_sum_stats, x_0=None):
         super().initialize(t, get_all_sum_stats, x_0)
         if self.cov is None:
             self.cov = np.eye(sum(np.size(x_0[k]) for k in self.keys))
         self.cov = np.array(self.cov)
+        self._dev_cache = None
         import scipy.stats
         self.rv = scipy.stats.multivariate_normal(
             mean=np.zeros(self.cov.shape[0]), cov=self.cov)
@@ -452,6 +458,39 @@ class NormalKernel(StochasticKernel):
         if self.ret_scale == SCALE_LIN:
             return self.rv.pdf(diff)
         return self.rv.logpdf(diff)
+
+    # --- batch (device) interface -----------------------------------------
+    def batch_unsupported_reason(self, x_0):
+        if self.ret_scale == SCALE_LIN:
+            return "NormalKernel with ret_scale SCALE_LIN"
+        if any(np.size(x_0[k]) != 1 for k in self.keys):
+            return "array-valued summary statistics"
+        return None
+
+    def device_params(self, t, x_0):
+        """(keys, x0[S], U[S, R], KERNEL_NORMAL_FULL, c) for the batch
+        kernel, in the kernel's key order; c = rank log(2 pi) + log_pdet."""
+        if self._dev_cache is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+            U, rank, log_pdet = K.psd_whitening(self.cov)
+            self._dev_cache = (
+                list(self.keys),
+                torch.as_tensor(_flat(x_0, self.keys), device=dev),
+                torch.as_tensor(np.ascontiguousarray(U), device=dev),
+                K.KERNEL_NORMAL_FULL,
+                float(rank * np.log(2 * np.pi) + log_pdet))
+        return self._dev_cache
+
+    def batch(self, stats_T, t, x_0, eps=np.inf, n=None, keys=None):
+        """Log-densities of n stat-major columns whose rows are the
+        statistics ``keys`` (default: the kernel's key order)."""
+        why = self.batch_unsupported_reason(x_0)
+        if why is not None:
+            raise ValueError(f"NormalKernel.batch: {why}")
+        dkeys, x0d, Ud, _, c = self.device_params(t, x_0)
+        stats_T = _rows_in_order(stats_T, keys, dkeys)
+        pd, _, _, _ = K.normal_kernel(stats_T, x0d, Ud, c, B=n)
+        return pd, None, None
 
 
 class _IndependentKernel(StochasticKernel):

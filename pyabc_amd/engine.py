@@ -542,8 +542,9 @@ class PNormAcceptance:
 
 
 class StochasticAcceptance:
-    """StochasticAcceptor over an independent normal / Laplace kernel
-    (acceptor/acceptor.py:440-473, distance/kernel.py:256-357): the log
+    """StochasticAcceptor over an independent normal / Laplace kernel or a
+    full-covariance normal kernel (kind 2, prm = U [S, R])
+    (acceptor/acceptor.py:440-473, distance/kernel.py:173-357): the log
     density, u ~ U[0,1) from Philox keyed by the GLOBAL evaluation id, the
     decision acc >= u and the acceptance weight, in one fused kernel."""
 
@@ -555,10 +556,15 @@ class StochasticAcceptance:
         self.apply_iw = apply_importance_weighting
 
     def __call__(self, stats, nv, seed, stream, eval_off):
-        pd, acc, accw, guard = K.stochastic_kernel(
-            stats, self.x0, self.prm, self.kind, self.c, B=nv,
-            pdf_norm=self.pdf_norm, inv_temp=self.inv_temp,
-            apply_iw=self.apply_iw, seed=seed, stream=stream, offset=eval_off)
+        kw = dict(B=nv, pdf_norm=self.pdf_norm, inv_temp=self.inv_temp,
+                  apply_iw=self.apply_iw, seed=seed, stream=stream,
+                  offset=eval_off)
+        if self.kind == K.KERNEL_NORMAL_FULL:   # prm = whitening factor U
+            pd, acc, accw, guard = K.normal_kernel(
+                stats, self.x0, self.prm, self.c, **kw)
+        else:
+            pd, acc, accw, guard = K.stochastic_kernel(
+                stats, self.x0, self.prm, self.kind, self.c, **kw)
         return pd, acc, guard, accw
 
 

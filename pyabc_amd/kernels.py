@@ -771,6 +771,7 @@ def sim_gaussian_mean(theta, sigma, seed, sid, offset, out=None, B=None):
 # ---------------------------------------------------------------------------
 KERNEL_NORMAL = 0
 KERNEL_LAPLACE = 1
+KERNEL_NORMAL_FULL = 2
 
 
 def stochastic_kernel(stats_T, x0, prm, kind, c, B=None, pdf_norm=None,
@@ -790,6 +791,34 @@ def stochastic_kernel(stats_T, x0, prm, kind, c, B=None, pdf_norm=None,
         guard = torch.empty(B, dtype=torch.uint8, device=_dev())
     call("abc_stochastic_kernel_f64", ptr(stats_T), ld, ptr(_contig(x0, F64)),
          ptr(_contig(prm, F64)), S, int(kind), float(c), B, ptr(pd),
+         float(pdf_norm if pdf_norm is not None else 0.0), float(inv_temp),
+         1 if apply_iw else 0, ptr(None if u is None else _contig(u, F64)),
+         int(seed), int(stream), int(offset), ptr(acc), ptr(accw), ptr(guard),
+         nat.stream())
+    return pd, acc, accw, guard
+
+
+def normal_kernel(stats_T, x0, U, c, B=None, pdf_norm=None, inv_temp=1.0,
+                  apply_iw=True, u=None, seed=0, stream=0, offset=0):
+    """Log-densities of a full-covariance normal kernel per column of
+    stat-major ``stats_T`` ([S, ld]): -0.5 (c + |(x - x0) U|^2) with the
+    whitening factor ``U`` [S, R] and c = rank log(2 pi) + log_pdet of
+    :func:`psd_whitening`; with ``pdf_norm`` also the fused stochastic
+    acceptance.  Returns (pd, accept, accw, guard)."""
+    S = stats_T.shape[0]
+    U = _contig(U, F64)
+    if U.dim() != 2 or U.shape[0] != S:
+        raise ValueError(f"U must be [S={S}, R], got {tuple(U.shape)}")
+    stats_T, ld, n = _stat_major(stats_T)
+    B = n if B is None else B
+    pd = torch.empty(B, dtype=F64, device=_dev())
+    acc = accw = guard = None
+    if pdf_norm is not None:
+        acc = torch.empty(B, dtype=torch.uint8, device=_dev())
+        accw = torch.empty(B, dtype=F64, device=_dev())
+        guard = torch.empty(B, dtype=torch.uint8, device=_dev())
+    call("abc_normal_kernel_f64", ptr(stats_T), ld, ptr(_contig(x0, F64)),
+         ptr(U), S, U.shape[1], float(c), B, ptr(pd),
          float(pdf_norm if pdf_norm is not None else 0.0), float(inv_temp),
          1 if apply_iw else 0, ptr(None if u is None else _contig(u, F64)),
          int(seed), int(stream), int(offset), ptr(acc), ptr(accw), ptr(guard),

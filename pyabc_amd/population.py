@@ -286,7 +286,9 @@ class ColumnarPopulation:
         callable is called once per particle on host copies."""
         f = distance_to_ground_truth
         if isinstance(f, DistanceToGroundTruth) and \
-                hasattr(f.distance, "batch") and torch.cuda.is_available():
+                hasattr(f.distance, "batch") and torch.cuda.is_available() \
+                and getattr(f.distance, "batch_unsupported_reason",
+                            lambda x_0: None)(f.x_0) is None:
             if self.stats_T is None:
                 raise ValueError("statistics of this population were not "
                                  "kept")

@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 from .base import Sampler, Sample
-from ..distance import DeviceStats, PNormDistance, _IndependentKernel
+from ..distance import (DeviceStats, PNormDistance, NormalKernel,
+                        _IndependentKernel)
 from ..distributed import Comm
 from ..engine import GenerationEngine, StochasticAcceptance
 from ..population import ColumnarPopulation
@@ -63,9 +64,10 @@ class BatchSpec:
         if getattr(self.summary_statistics, "__name__", "") != "identity":
             return "custom summary_statistics"
         if self.kind == "smc" and self.stochastic():
-            if not isinstance(self.distance, _IndependentKernel):
-                return ("StochasticAcceptor kernel is not an Independent"
-                        "Normal/LaplaceKernel")
+            if not isinstance(self.distance,
+                              (_IndependentKernel, NormalKernel)):
+                return ("StochasticAcceptor kernel is not a NormalKernel or "
+                        "an Independent Normal/LaplaceKernel")
             why = self.distance.batch_unsupported_reason(self.x_0)
             if why is not None:
                 return why

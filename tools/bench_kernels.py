@@ -68,11 +68,40 @@ def report(name, t, units, unit, per_unit, bound, extra=None):
     return row
 
 
+def bench_normal_kernel(B=1 << 20, calls=20):
+    """abc_normal_kernel_f64 with the fused acceptance, alone: `calls`
+    launches between two events (the allocations of the outputs overlap the
+    previous launch), best of 5.  2 S R FLOP against the measured MFMA rate
+    (tools/probes/mfma_f64_rate.hip) and 8 S + 18 bytes against HBM."""
+    g = torch.Generator(device="cuda").manual_seed(3)
+    for S in (64, 256):
+        R = S
+        stats = torch.randn((S, B), dtype=F64, device="cuda", generator=g)
+        x0 = torch.randn(S, dtype=F64, device="cuda", generator=g)
+        U = torch.randn((S, R), dtype=F64, device="cuda", generator=g) / S ** 0.5
+
+        def run():
+            for _ in range(calls):
+                K.normal_kernel(stats, x0, U, 1.0, pdf_norm=-0.5 * S,
+                                inv_temp=0.1, seed=1, stream=9)
+        t = timed(run) / calls
+        report("normal_kernel_accept_f64", t, B, "evaluations", 2 * S * R,
+               "mfma_f64", {"S": S, "R": R, "mfma_probe_tflops": 43.0,
+                            "bytes_per_eval": 8 * S + 18,
+                            "GB_per_s": B * (8 * S + 18) / t / 1e9})
+        del stats
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--normal-kernel", action="store_true",
+                    help="only the full-covariance normal kernel's rows")
     args = ap.parse_args()
     torch.cuda.set_device(0)
+    if args.normal_kernel:
+        bench_normal_kernel()
+        return
     g = torch.Generator(device="cuda").manual_seed(0)
     q = 4 if args.quick else 1
 
