@@ -513,6 +513,33 @@ int abc_normal_kernel_f64(const double* stats_T, int64_t ld, const double* x0,
                           const double* u, uint64_t seed, uint64_t stream,
                           uint64_t offset, uint8_t* accept, double* accw,
                           uint8_t* guard, hipStream_t stream_);
+/* Count-data kernels (stochastic_count.hip); replace BinomialKernel /
+ * PoissonKernel / NegativeBinomialKernel.__call__, distance/kernel.py:365-537
+ * (SCALE_LOG): the sum over s of scipy.stats logpmf with
+ * n = trunc(stats_T[s ld + b]), k = trunc(x0[s]), lf(m) = lgamma(m + 1):
+ *   kind 3 binomial: lf(n) - lf(k) - lf(n-k) + xlogy(k, p) + xlog1py(n-k, -p)
+ *   kind 4 Poisson : xlogy(k, n) - n - lf(k)
+ *   kind 5 negbin  : lf(k+n-1) - lf(k) - lf(n-1) + n log p + xlog1py(k, -p)
+ * log_p = log(p) and log1m_p = log1p(-p) come from the host (-inf allowed);
+ * kind 4 ignores p.  Out of support as scipy: NaN for a non-finite statistic,
+ * |x| >= 2^52, n < 0 (3, 4), n <= 0 or p = 0 (5); else -inf for k < 0, k > n
+ * or a nonzero count times log 0; a zero count times log 0 is 0.
+ * table: abc_count_table_bytes() bytes of caller-owned workspace, filled once
+ * per device by abc_count_table_init_f64: lf(m) then log(m) for m < 4096, each
+ * correctly rounded (log(0) is stored as 0).  Larger counts take a Stirling
+ * series.  Error <= (4.5 + S) 2^-53 sum_s sum_terms |term|.
+ * pd[b] depends on column b, x0, p and kind only.  The fused acceptance
+ * (accept != NULL), u, Philox and guard are those of
+ * abc_stochastic_kernel_f64.  1 <= S <= 4096, ld >= B. */
+size_t abc_count_table_bytes(void);
+int abc_count_table_init_f64(double* table, hipStream_t stream);
+int abc_count_kernel_f64(const double* stats_T, int64_t ld, const double* x0,
+                         int S, int kind, double p, double log_p,
+                         double log1m_p, const double* table, int64_t B,
+                         double* pd, double pdf_norm, double inv_temp,
+                         int apply_iw, const double* u, uint64_t seed,
+                         uint64_t stream, uint64_t offset, uint8_t* accept,
+                         double* accw, uint8_t* guard, hipStream_t stream_);
 /* StochasticAcceptor decision for given densities, SCALE_LOG (log_scale=1)
  * or SCALE_LIN: acc = (pd / pdf_norm) ** inv_temp.   acceptor/acceptor.py:456-473 */
 int abc_stochastic_accept_f64(const double* pd, int64_t B, double pdf_norm,

@@ -204,6 +204,12 @@ _SIGS = {
                                       c_int, c_dbl, c_i64, c_ptr, c_dbl,
                                       c_dbl, c_int, c_ptr, c_u64, c_u64,
                                       c_u64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "abc_count_table_bytes": (c_size, []),
+    "abc_count_table_init_f64": (c_int, [c_ptr, c_ptr]),
+    "abc_count_kernel_f64": (c_int, [c_ptr, c_i64, c_ptr, c_int, c_int, c_dbl,
+                                     c_dbl, c_dbl, c_ptr, c_i64, c_ptr, c_dbl,
+                                     c_dbl, c_int, c_ptr, c_u64, c_u64, c_u64,
+                                     c_ptr, c_ptr, c_ptr, c_ptr]),
     "abc_stochastic_accept_f64": (c_int, [c_ptr, c_i64, c_dbl, c_dbl, c_int,
                                           c_int, c_ptr, c_u64, c_u64, c_u64,
                                           c_ptr, c_ptr, c_ptr, c_ptr]),

@@ -106,6 +106,7 @@ int preload_distance();
 int preload_select();
 int preload_stochastic();
 int preload_stochastic_full();
+int preload_stochastic_count();
 int preload_local();
 int preload_local_pdf32();
 int preload_sort();

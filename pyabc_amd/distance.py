@@ -362,7 +362,8 @@ class AdaptivePNormDistance(PNormDistance):
 # stochastic kernels (distance/kernel.py:1-588): densities for the
 # StochasticAcceptor.  Independent normal / Laplace kernels evaluate through
 # abc_stochastic_kernel_f64 (single calls and the batch sampler alike); the
-# full-covariance NormalKernel's batches through abc_normal_kernel_f64.
+# full-covariance NormalKernel's batches through abc_normal_kernel_f64, the
+# count-data kernels' batches through abc_count_kernel_f64.
 # ---------------------------------------------------------------------------
 SCALE_LIN = "SCALE_LIN"
 SCALE_LOG = "SCALE_LOG"
@@ -607,7 +608,10 @@ class IndependentLaplaceKernel(_IndependentKernel):
 
 class _DiscreteKernel(StochasticKernel):
     """Count-data likelihoods (kernel.py:360-560), scipy.stats pmfs of the
-    observed counts given the simulated ones (host, closure sampler path)."""
+    observed counts given the simulated ones.  Single calls evaluate on the
+    host with scipy; batches of SCALE_LOG log-pmf sums on the device
+    (``kernels.count_kernel``)."""
+    _kind = None
 
     def __init__(self, p=None, ret_scale=SCALE_LOG, keys=None, pdf_max=None):
         super().__init__(ret_scale=ret_scale, keys=keys, pdf_max=pdf_max)
@@ -632,9 +636,41 @@ class _DiscreteKernel(StochasticKernel):
             return np.prod(dist.pmf(**args))
         return np.sum(dist.logpmf(**args))
 
+    # --- batch (device) interface -----------------------------------------
+    def batch_unsupported_reason(self, x_0):
+        name = type(self).__name__
+        if self.ret_scale == SCALE_LIN:
+            return f"{name} with ret_scale SCALE_LIN"
+        if callable(self.p):
+            return "kernel parameters depend on the particle parameters"
+        if any(np.size(x_0[k]) != 1 for k in self.keys):
+            return "array-valued summary statistics"
+        return None
+
+    def device_params(self, t, x_0):
+        """(keys, x0[S], [p], kind, 0.0) for the batch kernel, in the
+        kernel's key order; p stays on the host (its logarithms are kernel
+        arguments)."""
+        dev = torch.device("cuda", torch.cuda.current_device())
+        return (list(self.keys),
+                torch.as_tensor(_flat(x_0, self.keys), device=dev),
+                [0.5 if self.p is None else float(self.p)], self._kind, 0.0)
+
+    def batch(self, stats_T, t, x_0, eps=np.inf, n=None, keys=None):
+        """Log-pmf sums of n stat-major columns whose rows are the
+        statistics ``keys`` (default: the kernel's key order)."""
+        why = self.batch_unsupported_reason(x_0)
+        if why is not None:
+            raise ValueError(f"{type(self).__name__}.batch: {why}")
+        dkeys, x0d, prm, kind, _ = self.device_params(t, x_0)
+        stats_T = _rows_in_order(stats_T, keys, dkeys)
+        pd, _, _, _ = K.count_kernel(stats_T, x0d, prm[0], kind, B=n)
+        return pd, None, None
+
 
 class BinomialKernel(_DiscreteKernel):
     """binom.pmf(k=x_0, n=x, p) (kernel.py:360-419)."""
+    _kind = K.KERNEL_BINOMIAL
 
     def __init__(self, p, ret_scale=SCALE_LOG, keys=None, pdf_max=None):
         super().__init__(p, ret_scale, keys, pdf_max)
@@ -652,6 +688,7 @@ class BinomialKernel(_DiscreteKernel):
 
 class PoissonKernel(_DiscreteKernel):
     """poisson.pmf(k=x_0, mu=x) (kernel.py:422-470)."""
+    _kind = K.KERNEL_POISSON
 
     def __init__(self, ret_scale=SCALE_LOG, keys=None, pdf_max=None):
         super().__init__(None, ret_scale, keys, pdf_max)
@@ -671,6 +708,7 @@ class PoissonKernel(_DiscreteKernel):
 
 class NegativeBinomialKernel(_DiscreteKernel):
     """nbinom.pmf(k=x_0, n=x, p) (kernel.py:473-529)."""
+    _kind = K.KERNEL_NEGBINOMIAL
 
     def __init__(self, p, ret_scale=SCALE_LOG, keys=None, pdf_max=None):
         super().__init__(p, ret_scale, keys, pdf_max)

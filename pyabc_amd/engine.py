@@ -543,8 +543,9 @@ class PNormAcceptance:
 
 class StochasticAcceptance:
     """StochasticAcceptor over an independent normal / Laplace kernel or a
-    full-covariance normal kernel (kind 2, prm = U [S, R])
-    (acceptor/acceptor.py:440-473, distance/kernel.py:173-357): the log
+    full-covariance normal kernel (kind 2, prm = U [S, R]) or a count-data
+    kernel (kinds 3-5, prm = [p])
+    (acceptor/acceptor.py:440-473, distance/kernel.py:173-537): the log
     density, u ~ U[0,1) from Philox keyed by the GLOBAL evaluation id, the
     decision acc >= u and the acceptance weight, in one fused kernel."""
 
@@ -562,6 +563,9 @@ class StochasticAcceptance:
         if self.kind == K.KERNEL_NORMAL_FULL:   # prm = whitening factor U
             pd, acc, accw, guard = K.normal_kernel(
                 stats, self.x0, self.prm, self.c, **kw)
+        elif self.kind >= K.KERNEL_BINOMIAL:    # prm = [p], a host scalar
+            pd, acc, accw, guard = K.count_kernel(
+                stats, self.x0, self.prm[0], self.kind, **kw)
         else:
             pd, acc, accw, guard = K.stochastic_kernel(
                 stats, self.x0, self.prm, self.kind, self.c, **kw)

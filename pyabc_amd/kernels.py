@@ -772,6 +772,9 @@ def sim_gaussian_mean(theta, sigma, seed, sid, offset, out=None, B=None):
 KERNEL_NORMAL = 0
 KERNEL_LAPLACE = 1
 KERNEL_NORMAL_FULL = 2
+KERNEL_BINOMIAL = 3
+KERNEL_POISSON = 4
+KERNEL_NEGBINOMIAL = 5
 
 
 def stochastic_kernel(stats_T, x0, prm, kind, c, B=None, pdf_norm=None,
@@ -819,6 +822,51 @@ def normal_kernel(stats_T, x0, U, c, B=None, pdf_norm=None, inv_temp=1.0,
         guard = torch.empty(B, dtype=torch.uint8, device=_dev())
     call("abc_normal_kernel_f64", ptr(stats_T), ld, ptr(_contig(x0, F64)),
          ptr(U), S, U.shape[1], float(c), B, ptr(pd),
+         float(pdf_norm if pdf_norm is not None else 0.0), float(inv_temp),
+         1 if apply_iw else 0, ptr(None if u is None else _contig(u, F64)),
+         int(seed), int(stream), int(offset), ptr(acc), ptr(accw), ptr(guard),
+         nat.stream())
+    return pd, acc, accw, guard
+
+
+_COUNT_TABLES = {}
+
+
+def count_table():
+    """The count kernels' device table [2, T]: row 0 lgamma(m + 1), row 1
+    log(m) (entry 0 stored as 0) for m < T, built once per device."""
+    d = torch.cuda.current_device()
+    t = _COUNT_TABLES.get(d)
+    if t is None:
+        n = nat.lib().abc_count_table_bytes() // 8
+        t = torch.empty((2, n // 2), dtype=F64, device=_dev())
+        call("abc_count_table_init_f64", ptr(t), nat.stream())
+        _COUNT_TABLES[d] = t
+    return t
+
+
+def count_kernel(stats_T, x0, p, kind, B=None, pdf_norm=None, inv_temp=1.0,
+                 apply_iw=True, u=None, seed=0, stream=0, offset=0):
+    """Log-pmf sums of a binomial / Poisson / negative binomial kernel
+    (``kind`` 3 / 4 / 5) per column of stat-major ``stats_T`` ([S, ld]), the
+    statistics and ``x0`` truncated to integers as scipy's logpmf sees them;
+    ``p`` is the scalar success probability (ignored by Poisson).  With
+    ``pdf_norm`` also the fused stochastic acceptance.  Returns
+    (pd, accept, accw, guard)."""
+    S = stats_T.shape[0]
+    stats_T, ld, n = _stat_major(stats_T)
+    B = n if B is None else B
+    p = 0.5 if kind == KERNEL_POISSON else float(p)
+    with np.errstate(divide="ignore"):
+        log_p, log1m_p = float(np.log(p)), float(np.log1p(-p))
+    pd = torch.empty(B, dtype=F64, device=_dev())
+    acc = accw = guard = None
+    if pdf_norm is not None:
+        acc = torch.empty(B, dtype=torch.uint8, device=_dev())
+        accw = torch.empty(B, dtype=F64, device=_dev())
+        guard = torch.empty(B, dtype=torch.uint8, device=_dev())
+    call("abc_count_kernel_f64", ptr(stats_T), ld, ptr(_contig(x0, F64)), S,
+         int(kind), p, log_p, log1m_p, ptr(count_table()), B, ptr(pd),
          float(pdf_norm if pdf_norm is not None else 0.0), float(inv_temp),
          1 if apply_iw else 0, ptr(None if u is None else _contig(u, F64)),
          int(seed), int(stream), int(offset), ptr(acc), ptr(accw), ptr(guard),

@@ -19,7 +19,7 @@ import torch
 
 from .base import Sampler, Sample
 from ..distance import (DeviceStats, PNormDistance, NormalKernel,
-                        _IndependentKernel)
+                        _IndependentKernel, _DiscreteKernel)
 from ..distributed import Comm
 from ..engine import GenerationEngine, StochasticAcceptance
 from ..population import ColumnarPopulation
@@ -65,9 +65,11 @@ class BatchSpec:
             return "custom summary_statistics"
         if self.kind == "smc" and self.stochastic():
             if not isinstance(self.distance,
-                              (_IndependentKernel, NormalKernel)):
-                return ("StochasticAcceptor kernel is not a NormalKernel or "
-                        "an Independent Normal/LaplaceKernel")
+                              (_IndependentKernel, NormalKernel,
+                               _DiscreteKernel)):
+                return ("StochasticAcceptor kernel is not a NormalKernel, an "
+                        "Independent Normal/LaplaceKernel or a Binomial/"
+                        "Poisson/NegativeBinomialKernel")
             why = self.distance.batch_unsupported_reason(self.x_0)
             if why is not None:
                 return why

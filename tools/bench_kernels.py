@@ -92,15 +92,55 @@ def bench_normal_kernel(B=1 << 20, calls=20):
         del stats
 
 
+def bench_count_kernel(B=1 << 20, calls=10):
+    """abc_count_kernel_f64 with the fused acceptance, alone, per kind at
+    S = 16 and 256, once with every count below the table size T = 4096 (LDS
+    table branch) and once with every count above it (Stirling / log branch).
+    Reports the element rate (S B / t), the HBM rate its 8 S + 18 bytes per
+    evaluation imply, and for the table branch the fp64 instruction rate from
+    the per-element count read off the source (trunc, subtractions, two
+    TwoSums and their compensation adds: 17 binomial, 18 negative binomial;
+    trunc, fma, add: 3 Poisson).  The Stirling branch's libm log is not
+    counted, so that row carries no instruction rate."""
+    g = torch.Generator(device="cuda").manual_seed(4)
+    ops = {K.KERNEL_BINOMIAL: 17, K.KERNEL_POISSON: 3, K.KERNEL_NEGBINOMIAL: 18}
+    K.count_table()
+    for S in (16, 256):
+        x0 = torch.randint(1, 40, (S,), device="cuda", generator=g).to(F64)
+        for branch, lo, hi in (("table", 40, 2000), ("stirling", 5000, 10 ** 6)):
+            stats = torch.randint(lo, hi, (S, B), device="cuda",
+                                  generator=g).to(F64)
+            for kind, name in ((K.KERNEL_BINOMIAL, "binomial"),
+                               (K.KERNEL_POISSON, "poisson"),
+                               (K.KERNEL_NEGBINOMIAL, "negbinomial")):
+                def run():
+                    for _ in range(calls):
+                        K.count_kernel(stats, x0, 0.3, kind, pdf_norm=-3.0 * S,
+                                       inv_temp=0.1, seed=1, stream=9)
+                t = timed(run) / calls
+                extra = {"S": S, "kind": name, "branch": branch,
+                         "elements_per_s": S * B / t}
+                if branch == "table":
+                    extra["fp64_Tops_per_s"] = S * B * ops[kind] / t / 1e12
+                report("count_kernel_accept_f64", t, B, "evaluations",
+                       8 * S + 18, "hbm", extra)
+            del stats
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--normal-kernel", action="store_true",
                     help="only the full-covariance normal kernel's rows")
+    ap.add_argument("--count-kernel", action="store_true",
+                    help="only the count-data kernels' rows")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     if args.normal_kernel:
         bench_normal_kernel()
+        return
+    if args.count_kernel:
+        bench_count_kernel()
         return
     g = torch.Generator(device="cuda").manual_seed(0)
     q = 4 if args.quick else 1
