@@ -277,6 +277,30 @@ int abc_importance_weights_f64(const double* logpd, const double* prior,
                                double prior_const, int64_t M, double* w,
                                hipStream_t stream);
 
+/* Cross-validated KDE log-likelihood over a grid of bandwidth scalings: the
+ * k G fits and k G density passes sklearn's GridSearchCV runs over
+ * MultivariateNormalTransition.scaling, as one pass over the pairs
+ *                                    transition/model_selection.py:9-69
+ *                                    (Transition.score, base.py:106-107;
+ *                                     pdf, multivariatenormal.py:102-125)
+ * Folds are the contiguous row ranges [fold_off[f], fold_off[f+1]); fold f's
+ * rows are scored against all other rows, whitened z = (x - mu[f]) Us[f] by
+ * the fold's training covariance at scaling 1 (Us[f] = scipy's _PSD factor,
+ * [d][d] row-major, full rank).  coef[g] = log2(e) / (2 s_g).
+ *   out_L[g][i]     = ln sum_{j not in fold(i)} w_j exp(-|z_i - z_j|^2 / (2 s_g))
+ *   out_score[f][g] = sum_{i in f} w_i out_L[g][i]   (fixed order)
+ * (the caller adds -(d ln 2 pi + log_pdet_f + d ln s_g)/2 sum_{i in f} w_i).
+ * d <= 32, 1 <= G <= 8 per call, 2 <= k <= n.  All pointers are device
+ * pointers EXCEPT fold_off, a host array of k + 1 offsets that is validated
+ * on the host and copied to the workspace with hipMemcpyAsync (so the call is
+ * not graph-capturable).  Results are bit-identical from run to run. */
+size_t abc_kde_cv_workspace_bytes(int64_t n, int d, int k, int G);
+int abc_kde_cv_f64(const double* X, const double* w, int64_t n, int d,
+                   const int64_t* fold_off, int k, const double* mu,
+                   const double* Us, const double* coef, int G, double* out_L,
+                   double* out_score, void* ws, size_t ws_bytes,
+                   hipStream_t stream);
+
 /* ---------------- (a4) weight normalisation / ESS ------------------------
  * Replaces Population._normalize_weights            population.py:120-142
  * and effective_sample_size                         weighted_statistics.py:73-83 */

@@ -52,7 +52,7 @@ from .sampler import (Sample, SampleFactory, Sampler,  # noqa: E402
                       SingleCoreSampler, GPUBatchSampler)
 from .storage import History, create_sqlite_db_id  # noqa: E402
 from .transition import (Transition, MultivariateNormalTransition,  # noqa: E402
-                         LocalTransition, NotEnoughParticles,
+                         LocalTransition, GridSearchCV, NotEnoughParticles,
                          silverman_rule_of_thumb, scott_rule_of_thumb)
 from .smc import ABCSMC  # noqa: E402
 from . import weighted_statistics  # noqa: E402

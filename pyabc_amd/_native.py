@@ -114,6 +114,10 @@ _SIGS = {
                                          c_dbl, c_ptr, c_ptr, c_size, c_ptr]),
     "abc_importance_weights_f64": (c_int, [c_ptr, c_ptr, c_dbl, c_i64, c_ptr,
                                            c_ptr]),
+    "abc_kde_cv_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
+    "abc_kde_cv_f64": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_int,
+                               c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr,
+                               c_ptr, c_size, c_ptr]),
     # (a4)
     "abc_reduce_workspace_bytes": (c_size, []),
     "abc_sum_f64": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr]),

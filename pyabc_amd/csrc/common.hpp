@@ -102,6 +102,7 @@ inline int preload_kernel(F* f) {
 int preload_propose();
 int preload_kde();
 int preload_kde_mfma();
+int preload_kde_cv();
 int preload_distance();
 int preload_select();
 int preload_stochastic();

@@ -474,6 +474,50 @@ class PackedPopulation:
         return int(ws[off + 4:off + 8].view(torch.int32).item())
 
 
+KDE_CV_MAX_G = 8     # grid values one abc_kde_cv_f64 launch serves
+
+
+def kde_cv(X, w, fold_off, mu, Us, scalings):
+    """Cross-validated KDE log-sums for a grid of scalings (kde_cv.hip).
+
+    X [n, d], w [n] (raw weights), mu [k, d] and Us [k, d, d] (per fold the
+    training mean and the whitening of the training covariance at scaling
+    1) on the device; ``fold_off`` k + 1 host offsets, ``scalings`` G host
+    values.  Returns (L [G, n], score [k, G]): L[g, i] = ln sum over the rows
+    outside i's fold of w_j exp(-|z_i - z_j|^2 / (2 s_g)) and score[f, g] =
+    sum_{i in f} w_i L[g, i].  Grids above KDE_CV_MAX_G go in chunks."""
+    X = _contig(X, F64)
+    w = _contig(w, F64)
+    mu = _contig(mu, F64)
+    Us = _contig(Us, F64)
+    n, d = X.shape
+    off = [int(o) for o in fold_off]
+    k = len(off) - 1
+    if mu.shape != (k, d) or Us.shape != (k, d, d):
+        raise ValueError("kde_cv: mu / Us do not match the folds")
+    s = np.asarray(scalings, dtype=np.float64).ravel()
+    G = s.size
+    coef = torch.as_tensor(LOG2E / (2.0 * s), dtype=F64, device=_dev())
+    L = torch.empty((G, n), dtype=F64, device=_dev())
+    score = torch.empty((k, G), dtype=F64, device=_dev())
+    c_off = (ctypes.c_int64 * (k + 1))(*off)
+    for g0 in range(0, G, KDE_CV_MAX_G):
+        gn = min(KDE_CV_MAX_G, G - g0)
+        wsb = nat.lib().abc_kde_cv_workspace_bytes(n, d, k, gn)
+        if wsb == 0:
+            raise nat.NativeLibraryError(
+                f"kde_cv: unsupported shape n={n} d={d} k={k}")
+        ws = WS.get(wsb, "kde_cv")
+        sc = score if gn == G else torch.empty((k, gn), dtype=F64,
+                                               device=_dev())
+        call("abc_kde_cv_f64", ptr(X), ptr(w), n, d, c_off, k, ptr(mu),
+             ptr(Us), ptr(coef[g0:]), gn, ptr(L[g0:]), ptr(sc), ptr(ws), wsb,
+             nat.stream())
+        if sc is not score:
+            score[:, g0:g0 + gn] = sc
+    return L, score
+
+
 def importance_weights(logpd, prior=None, prior_const=1.0):
     M = logpd.numel()
     w = torch.empty(M, dtype=F64, device=_dev())

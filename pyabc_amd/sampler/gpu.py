@@ -52,7 +52,8 @@ class BatchSpec:
 
     def unsupported_reason(self):
         from ..acceptor import UniformAcceptor
-        from ..transition import MultivariateNormalTransition, LocalTransition
+        from ..transition import (MultivariateNormalTransition,
+                                  LocalTransition, GridSearchCV)
         if len(self.models) != 1:
             return "model selection (several models)"
         if not isinstance(self.models[0], BatchModel):
@@ -80,9 +81,12 @@ class BatchSpec:
                     self.acceptor.use_complete_history:
                 return "acceptor is not UniformAcceptor(current time)"
         if self.kind == "smc":
+            tr = self.transitions[0]
+            if isinstance(tr, GridSearchCV):
+                # the search's winner is what proposes and weights
+                tr = getattr(tr, "best_estimator_", tr.estimator)
             if self.t > 0 and not isinstance(
-                    self.transitions[0],
-                    (MultivariateNormalTransition, LocalTransition)):
+                    tr, (MultivariateNormalTransition, LocalTransition)):
                 return "transition is not MultivariateNormal/LocalTransition"
         return None
 

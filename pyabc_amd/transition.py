@@ -2,12 +2,14 @@
 
 Reference: pyabc/transition/base.py:13-123 (Transition), transitionmeta.py:
 7-51 (no-parameter handling and fit-weight normalisation),
-multivariatenormal.py:42-125 (MultivariateNormalTransition) and
-local_transition.py:13-145 (LocalTransition).  fit / rvs / pdf compute through
+multivariatenormal.py:42-125 (MultivariateNormalTransition),
+local_transition.py:13-145 (LocalTransition) and model_selection.py:9-69
+(GridSearchCV).  fit / rvs / pdf compute through
 the HIP kernels (weighted moments, Philox proposals, KDE pass; kNN, local
 covariances, local density); only d x d factorisations run on the host, where
 the reference also calls numpy/scipy on d x d matrices.
 """
+import copy
 import functools
 import math
 from abc import ABCMeta, abstractmethod
@@ -24,7 +26,8 @@ from .engine import (DeviceMVNFit, _side_stream, start_cdf,
 from .frames import DeviceFrame, as_device_matrix, as_device_vector
 
 __all__ = ["Transition", "DiscreteTransition", "MultivariateNormalTransition",
-           "LocalTransition", "NotEnoughParticles", "silverman_rule_of_thumb",
+           "LocalTransition", "GridSearchCV", "kfold_offsets",
+           "NotEnoughParticles", "silverman_rule_of_thumb",
            "scott_rule_of_thumb"]
 
 
@@ -412,3 +415,196 @@ class _LocalDeviceFit:
     def logpdf(self, theta):
         return K.local_logpdf(theta, self.X, self.w, self._invs, self._dets,
                               self.kde_precision)
+
+
+def kfold_offsets(n, k):
+    """The k + 1 row offsets of sklearn's unshuffled KFold: contiguous folds
+    in row order, the first n % k of n // k + 1 rows, the rest of n // k."""
+    q, r = divmod(int(n), int(k))
+    return [f * q + min(f, r) for f in range(k + 1)]
+
+
+def _first_argmax(scores):
+    """Index of the first maximum (sklearn: rank 1 by ``min`` ranking)."""
+    return int(np.argmax(np.asarray(scores, dtype=np.float64)))
+
+
+def _take_rows(a, idx):
+    if isinstance(a, pd.DataFrame):
+        return a.iloc[idx]
+    if isinstance(a, DeviceFrame):
+        return DeviceFrame(a.tensor[torch.as_tensor(idx)], a.columns)
+    if isinstance(a, torch.Tensor):
+        return a[torch.as_tensor(idx)]
+    return np.asarray(a)[idx]
+
+
+class GridSearchCV:
+    """Select transition parameters by k-fold cross-validation of the
+    weighted log-likelihood ``Transition.score`` (model_selection.py:9-69,
+    there a thin adapter over ``sklearn.model_selection.GridSearchCV``;
+    sklearn is not needed here).
+
+    Defaults: ``estimator = MultivariateNormalTransition()``,
+    ``param_grid = {'scaling': np.linspace(0.05, 1.0, 5)}``, ``cv = 5``.
+    Folds are sklearn's unshuffled ``KFold`` (:func:`kfold_offsets`), the
+    mean test score is the plain mean over the folds and the first maximum
+    wins.  ``scoring``, ``n_jobs``, ``iid``, ``verbose``, ``pre_dispatch``,
+    ``error_score`` and ``return_train_score`` only steer sklearn's dispatch
+    and are accepted and ignored.  Train scores are NOT computed and
+    ``cv_results_`` carries no train keys: they would quadruple the pair
+    count for a number nothing reads.
+
+    A MultivariateNormalTransition searched over ``{'scaling': ...}`` runs
+    as one device pass (kernels.kde_cv): per fold the training moments come
+    from the fold slices' moments merged on the host, the training weights
+    are used as they are (not renormalised), and every pair's whitened
+    distance is computed once for the whole grid.  Any other estimator or
+    grid, more than 32 parameters, a training set of fewer than 2 rows, a
+    rank-deficient fold covariance or a host without a device take the
+    plain loop (deepcopy, set_params, fit, score).  The two paths differ in
+    one convention: the plain loop fits through ``Transition.fit``, which
+    renormalises each fold's training weights to sum 1 (transitionmeta.py:
+    17-18), so its effective sample size, hence its bandwidth, and its
+    density's scale are those of the normalised weights.  For the same
+    MultivariateNormalTransition the scores, and possibly the selected
+    scaling, therefore depend on which path ran.
+
+    Everything else (``rvs``, ``pdf``, ``device_fit``, ``logpdf_device``,
+    ``cov``, ``X``, ``w``, ...) is forwarded to ``best_estimator_``.
+    """
+
+    def __init__(self, estimator=None, param_grid=None, scoring=None,
+                 n_jobs=1, iid=True, refit=True, cv=5, verbose=0,
+                 pre_dispatch='2*n_jobs', error_score='raise',
+                 return_train_score=True):
+        if estimator is None:
+            estimator = MultivariateNormalTransition()
+        if param_grid is None:
+            param_grid = {'scaling': np.linspace(0.05, 1.0, 5)}
+        self.estimator = estimator
+        self.param_grid = param_grid
+        self.refit = refit
+        self.cv = cv
+
+    def __getattr__(self, item):
+        if item == "best_estimator_":
+            raise AttributeError(item)
+        return getattr(self.best_estimator_, item)
+
+    def _candidates(self):
+        names = sorted(self.param_grid)
+        cands = [{}]
+        for name in names:
+            cands = [dict(c, **{name: v}) for c in cands
+                     for v in self.param_grid[name]]
+        return cands
+
+    def fit(self, X, w):
+        n = len(X)
+        if n <= 1 or _ncols(X) == 0:
+            self.estimator.fit(X, w)
+            self.best_estimator_ = self.estimator
+            return self
+        if int(self.cv) < 2:
+            raise ValueError(f"cv must be at least 2, got {self.cv}")
+        k = min(int(self.cv), n)
+        off = kfold_offsets(n, k)
+        cands = self._candidates()
+        scores = None
+        if (isinstance(self.estimator, MultivariateNormalTransition)
+                and list(self.param_grid) == ['scaling']
+                and torch.cuda.is_available()):
+            scores = self._device_scores(X, w, off)
+        if scores is None:
+            scores = self._host_scores(X, w, off, cands)
+        mean = scores.mean(axis=0)
+        best = _first_argmax(mean)
+        self.best_index_ = best
+        self.best_params_ = cands[best]
+        self.best_score_ = float(mean[best])
+        res = {"params": cands, "mean_test_score": mean,
+               "std_test_score": scores.std(axis=0)}
+        for name in self.param_grid:
+            res["param_" + name] = np.array([c[name] for c in cands],
+                                            dtype=object)
+        for f in range(k):
+            res[f"split{f}_test_score"] = scores[f]
+        # sklearn's 'min' ranking: 1 + the number of strictly better ones
+        res["rank_test_score"] = np.array(
+            [1 + int(np.sum(mean > m)) for m in mean], dtype=np.int32)
+        self.cv_results_ = res
+        if self.refit:
+            est = copy.deepcopy(self.estimator).set_params(**cands[best])
+            est.fit(X, w)
+            self.best_estimator_ = est
+        return self
+
+    def _host_scores(self, X, w, off, cands):
+        n, k = off[-1], len(off) - 1
+        scores = np.empty((k, len(cands)))
+        for f in range(k):
+            test = np.arange(off[f], off[f + 1])
+            train = np.r_[0:off[f], off[f + 1]:n]
+            w_test = _take_rows(w, test)
+            if isinstance(w_test, torch.Tensor):
+                w_test = w_test.cpu().numpy()
+            for g, params in enumerate(cands):
+                est = copy.deepcopy(self.estimator).set_params(**params)
+                est.fit(_take_rows(X, train), _take_rows(w, train))
+                with np.errstate(divide="ignore"):
+                    scores[f, g] = est.score(_take_rows(X, test), w_test)
+        return scores
+
+    def _device_scores(self, X, w, off):
+        """score[f, g] of the MVN estimator over the scaling grid through
+        the cross-validation kernel, or None where it does not apply."""
+        Xd, _ = as_device_matrix(X)
+        wd = as_device_vector(w)
+        n, d = Xd.shape
+        k = len(off) - 1
+        sizes = np.diff(off)
+        if d > 32 or n - sizes.max() < 2:
+            return None
+        grid = np.asarray(list(self.param_grid['scaling']), dtype=np.float64)
+        # moments of the k fold slices, merged to each fold's complement on
+        # the host in fp64 (pairwise update of [sum w, sum w^2, mu, C])
+        mom = torch.stack([K.weighted_moments(Xd[off[f]:off[f + 1]],
+                                              wd[off[f]:off[f + 1]])
+                           for f in range(k)]).cpu().numpy()
+        bw_sel = self.estimator.bandwidth_selector
+        mu = np.empty((k, d))
+        Us = np.empty((k, d, d))
+        log_pdet = np.empty(k)
+        for f in range(k):
+            sw = sw2 = 0.0
+            m = np.zeros(d)
+            C = np.zeros((d, d))
+            for o in range(k):
+                b = mom[o, 0]
+                if o == f or not b > 0:
+                    continue
+                delta = mom[o, 2:2 + d] - m
+                C += mom[o, 2 + d:].reshape(d, d) + np.outer(delta, delta) * (
+                    sw * b / (sw + b))
+                m += delta * (b / (sw + b))
+                sw += b
+                sw2 += mom[o, 1]
+            fact = sw - sw2 / sw if sw > 0 else 0.0
+            if not fact > 0:
+                return None
+            cov1 = C / fact * bw_sel(1.0 / sw2, d) ** 2
+            U, rank, lp = K.psd_whitening(cov1)
+            if rank < d or not np.all(np.isfinite(U)):
+                return None
+            mu[f], Us[f], log_pdet[f] = m, U, lp
+        host = torch.as_tensor(np.concatenate([mu.ravel(), Us.ravel()]),
+                               device=Xd.device)
+        _, score = K.kde_cv(Xd, wd, off, host[:k * d].view(k, d),
+                            host[k * d:].view(k, d, d), grid)
+        # the Gaussian constant: c[f, g] sum_{i in f} w_i
+        wsum = mom[:, 0]
+        c = -0.5 * (d * K.LOG_2PI + log_pdet[:, None]
+                    + d * np.log(grid)[None, :])
+        with np.errstate(invalid="ignore"):
+            return score.cpu().numpy() + c * wsum[:, None]

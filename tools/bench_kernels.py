@@ -92,6 +92,42 @@ def bench_normal_kernel(B=1 << 20, calls=20):
         del stats
 
 
+def bench_kde_cv(n=100_000, d=8, k=5, G=5):
+    """abc_kde_cv_f64 alone (whitening, pair pass and merge of one call)
+    against the same search with the single-bandwidth entry points: k G times
+    DeviceMVNFit on the gathered training rows plus logpdf on the fold."""
+    from pyabc_amd.transition import kfold_offsets
+    g = torch.Generator(device="cuda").manual_seed(5)
+    X = torch.randn((n, d), dtype=F64, device="cuda", generator=g)
+    w = torch.rand(n, dtype=F64, device="cuda", generator=g) + 0.5
+    w /= w.sum()
+    off = kfold_offsets(n, k)
+    grid = np.linspace(0.05, 1.0, G)
+    mu = X.mean(0).repeat(k, 1)
+    Us = (torch.eye(d, dtype=F64, device="cuda") * 4.0).repeat(k, 1, 1)
+    pairs = sum((n - (off[f + 1] - off[f])) * (off[f + 1] - off[f])
+                for f in range(k))
+    t = timed(lambda: K.kde_cv(X, w, off, mu, Us, grid), reps=3)
+    # per pair: 2 d (Gram) + 3, per pair and grid value ~8 (exponent twice,
+    # maximum, shift, exponential, sum)
+    report("kde_cv_f64", t, pairs * G, "pair_grid_values", 8 + (2 * d + 3) / G,
+           "valu_f64", {"n": n, "d": d, "k": k, "G": G, "pairs": pairs})
+
+    def loop():
+        out = torch.empty((k, G), dtype=F64, device="cuda")
+        for f in range(k):
+            lo, hi = off[f], off[f + 1]
+            Xtr, wtr = torch.cat([X[:lo], X[hi:]]), torch.cat([w[:lo], w[hi:]])
+            for j, s in enumerate(grid):
+                fit = DeviceMVNFit(Xtr, wtr, s)
+                out[f, j] = (fit.logpdf(X[lo:hi]) * w[lo:hi]).sum()
+        return out
+    t2 = timed(loop, reps=3)
+    report("kde_cv_by_single_fits", t2, pairs * G, "pair_grid_values", 0.0,
+           "valu_f64", {"n": n, "d": d, "k": k, "G": G,
+                        "ratio_to_kde_cv": t2 / t})
+
+
 def bench_count_kernel(B=1 << 20, calls=10):
     """abc_count_kernel_f64 with the fused acceptance, alone, per kind at
     S = 16 and 256, once with every count below the table size T = 4096 (LDS
@@ -132,12 +168,18 @@ def main():
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--normal-kernel", action="store_true",
                     help="only the full-covariance normal kernel's rows")
+    ap.add_argument("--kde-cv", action="store_true",
+                    help="only the cross-validation kernel and its "
+                         "single-fit equivalent")
     ap.add_argument("--count-kernel", action="store_true",
                     help="only the count-data kernels' rows")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     if args.normal_kernel:
         bench_normal_kernel()
+        return
+    if args.kde_cv:
+        bench_kde_cv()
         return
     if args.count_kernel:
         bench_count_kernel()
