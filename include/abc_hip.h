@@ -497,6 +497,71 @@ int abc_sim_gaussian_mean_f64(const double* theta, int64_t B, double sigma,
                               uint64_t seed, uint64_t sid, uint64_t offset,
                               double* out, hipStream_t stream);
 
+/* ---------------- mass-action reaction-network ODE batch model ------------
+ * The model class of doc/examples/conversion_reaction.ipynb and noise.ipynb:
+ * dx/dt = sum_r nu_r k_r prod_(reactants of r) x, x(0) and k_r constants or
+ * columns of theta, observed at fixed times.  One lane integrates one
+ * proposal with the adaptive Dormand-Prince 5(4) pair and scipy RK45's
+ * controller (RMS error norm of err / (atol + rtol max(|x|, |x_new|)),
+ * safety 0.9, factor in [0.2, 10], no growth directly after a rejection,
+ * Hairer's first step); steps are clipped so that every observation time is
+ * hit exactly, and the step size carries over between observation intervals.
+ *
+ * The network is this fixed-size table.  It is HOST memory: the call copies
+ * it into the kernel's arguments, so it may be freed or changed as soon as
+ * the call returns.  Every index field is an int32.
+ *   rate_kind[r]   0: k_r = rate_const[r]; 1: k_r = theta[b][rate_col[r]];
+ *                  2: k_r = 10 ** theta[b][rate_col[r]]
+ *   reactant[r]    two slots, a species index or -1 (empty); "2A" fills both
+ *                  with A, so the propensity is k_r x_A x_A
+ *   pair_start     CSR offsets into pair[]: reaction r owns entries
+ *                  pair_start[r] .. pair_start[r + 1] - 1 (at most 128 in all)
+ *   pair[p]        one non-zero NET stoichiometric coefficient:
+ *                  species = pair[p] & 0xff, coefficient = pair[p] >> 8
+ *                  (arithmetic shift, a signed integer)
+ *   x_init_col[i]  -1: x_i(0) = x_init[i]; otherwise x_i(0) = theta[b][col]
+ *   observed[o]    species index of observed species o
+ *   t_obs[j]       strictly increasing, > 0
+ * Statistic s = o * n_times + j is species observed[o] at t_obs[j] (species
+ * blocks, time-major within a block): S = n_observed * n_times <= 256. */
+#define ABC_ODE_MAX_SPECIES 8
+#define ABC_ODE_MAX_REACTIONS 16
+#define ABC_ODE_MAX_PAIRS 128
+#define ABC_ODE_MAX_STATS 256
+typedef struct abc_ode_table {
+  int32_t n_species;   /* 1 .. 8 */
+  int32_t n_reactions; /* 1 .. 16 */
+  int32_t n_times;     /* >= 1 */
+  int32_t n_observed;  /* 1 .. n_species */
+  double rate_const[ABC_ODE_MAX_REACTIONS];
+  int32_t rate_kind[ABC_ODE_MAX_REACTIONS];
+  int32_t rate_col[ABC_ODE_MAX_REACTIONS];
+  int32_t reactant[ABC_ODE_MAX_REACTIONS][2];
+  int32_t pair_start[ABC_ODE_MAX_REACTIONS + 2]; /* [R + 1] used; padded */
+  int32_t pair[ABC_ODE_MAX_PAIRS];
+  double x_init[ABC_ODE_MAX_SPECIES];
+  int32_t x_init_col[ABC_ODE_MAX_SPECIES];
+  int32_t observed[ABC_ODE_MAX_SPECIES];
+  double t_obs[ABC_ODE_MAX_STATS];
+} abc_ode_table;
+/* out_T[s * ld + b] (stat-major, ld >= B) = statistic s of proposal b, plus
+ * sigma * z when sigma != 0, z the fast normal (offset + b) * S + s of the
+ * linear-Gaussian simulator's stream (seed, sid); no random number is drawn
+ * when sigma == 0.  A proposal that needs more than max_steps attempted
+ * steps, or whose error norm or step size stops being finite (or whose step
+ * falls under 10 ulp of t), gets +inf in all of its S statistics: the
+ * acceptance compares then reject it, and no other proposal is affected.
+ * A proposal's column does not depend on B, on its position b or on the
+ * other proposals of the call.  theta is [B][d], d <= 32.  steps_out (may be
+ * NULL) receives per proposal the number of attempted steps, rejected ones
+ * included: the proposal cost 2 + 6 steps right-hand-side evaluations. */
+int abc_sim_mass_action_ode_f64(const abc_ode_table* table, const double* theta,
+                                int64_t B, int d, double rtol, double atol,
+                                int64_t max_steps, double sigma, uint64_t seed,
+                                uint64_t sid, uint64_t offset, double* out_T,
+                                int64_t ld, int64_t* steps_out,
+                                hipStream_t stream);
+
 /* ---------------- (f3) exact inference: stochastic acceptance -------------
  * SURVEY 8(f) rank 3.  Replaces, per evaluation b (stat-major stats_T):
  *   IndependentNormalKernel.__call__  (kind 0, prm = var)  distance/kernel.py:256-282

@@ -238,7 +238,29 @@ _SIGS = {
                 c_i64, c_ptr]),
     "abc_sim_gaussian_mean_f64": (c_int, [c_ptr, c_i64, c_dbl, c_u64, c_u64,
                                           c_u64, c_ptr, c_ptr]),
+    # the first argument is a HOST pointer to an OdeTable (copied at launch)
+    "abc_sim_mass_action_ode_f64": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_dbl,
+                                            c_dbl, c_i64, c_dbl, c_u64, c_u64,
+                                            c_u64, c_ptr, c_i64, c_ptr,
+                                            c_ptr]),
 }
+
+
+class OdeTable(ctypes.Structure):
+    """``abc_ode_table`` of include/abc_hip.h (the layout is documented
+    there): the reaction network of abc_sim_mass_action_ode_f64."""
+    MAX_SPECIES, MAX_REACTIONS, MAX_PAIRS, MAX_STATS = 8, 16, 128, 256
+    _fields_ = [
+        ("n_species", ctypes.c_int32), ("n_reactions", ctypes.c_int32),
+        ("n_times", ctypes.c_int32), ("n_observed", ctypes.c_int32),
+        ("rate_const", c_dbl * 16), ("rate_kind", ctypes.c_int32 * 16),
+        ("rate_col", ctypes.c_int32 * 16),
+        ("reactant", (ctypes.c_int32 * 2) * 16),
+        ("pair_start", ctypes.c_int32 * 18), ("pair", ctypes.c_int32 * 128),
+        ("x_init", c_dbl * 8), ("x_init_col", ctypes.c_int32 * 8),
+        ("observed", ctypes.c_int32 * 8), ("t_obs", c_dbl * 256),
+    ]
+
 
 _lib = None
 _load_error = None

@@ -5,7 +5,9 @@ The reference evaluates one Python model call per proposal
 :class:`BatchModel` for the statistics of B proposals at once, stat-major
 ``[S, B]`` on the device.  The two synthetic models below are the benchmark
 models of BASELINE.json; each is one HIP kernel with
-Philox4x32-10 noise.
+Philox4x32-10 noise.  :class:`MassActionODEModel` is the model class of the
+reference's worked examples (doc/examples/conversion_reaction.ipynb,
+noise.ipynb): a reaction-network ODE integrated per proposal by one kernel.
 """
 import numpy as np
 import torch
@@ -114,6 +116,183 @@ class GaussianMeanModel(BatchModel):
     def simulate(self, theta, seed, sid, offset):
         out = K.sim_gaussian_mean(theta, self.sigma, seed, sid, offset)
         return out.view(1, -1)
+
+
+class MassActionODEModel(BatchModel):
+    """Mass-action kinetics ``dx/dt = sum_r nu_r k_r prod(reactants of r)``
+    observed at fixed times, integrated on the device with an adaptive
+    Dormand-Prince 5(4) pair (scipy ``RK45``'s controller), one lane per
+    proposal.
+
+    ``species``: 1 to 8 names.  ``reactions``: 1 to 16 entries ``(reactants,
+    products, rate)``; reactants and products are dicts ``name -> count``
+    (non-negative integers, at most two reactant molecules: ``{}``, ``{A: 1}``,
+    ``{A: 1, B: 1}``, ``{A: 2}``; the propensity of ``2A ->`` is ``k A A``);
+    ``rate`` is a float, ``("theta", j)`` (column j of theta) or
+    ``("log10theta", j)`` (``10 ** theta_j``).  ``x_init``: per species (a
+    sequence in species order, or a dict by name, missing names starting at
+    0) a float or ``("theta", j)``.
+    ``t_obs``: strictly increasing positive times; ``observed``: the observed
+    species (default all).
+
+    Statistics: species blocks in ``observed`` order, time-major within a
+    block -- statistic ``o * T + j`` is observed species o at ``t_obs[j]``,
+    default key ``f"{species}_{j:03d}"``; ``S = T * len(observed) <= 256``.
+    With ``sigma > 0`` the noise is :class:`LinearGaussianModel`'s (the same
+    Philox stream and fast normals).  A proposal whose integration needs more
+    than ``max_steps`` attempted steps or stops being finite has ``+inf`` in
+    every statistic, so it is rejected and never a NaN.
+    """
+
+    def __init__(self, species, reactions, x_init, t_obs, observed=None,
+                 sigma=0.0, rtol=1e-6, atol=1e-9, max_steps=100000, keys=None,
+                 name="mass_action_ode", x0=None):
+        from ._native import OdeTable
+        self.species = tuple(species)
+        n = len(self.species)
+        if not 1 <= n <= OdeTable.MAX_SPECIES or len(set(self.species)) != n:
+            raise ValueError(f"1 to {OdeTable.MAX_SPECIES} distinct species, "
+                             f"got {self.species}")
+        index = {s: i for i, s in enumerate(self.species)}
+
+        def sp(name_):
+            if name_ not in index:
+                raise ValueError(f"unknown species {name_!r}")
+            return index[name_]
+
+        def counts(side):
+            out = np.zeros(n, dtype=np.int64)
+            for k, c in dict(side).items():
+                if int(c) != c or c < 0:
+                    raise ValueError(f"stoichiometry of {k!r} must be a "
+                                     f"non-negative integer, got {c!r}")
+                out[sp(k)] += int(c)
+            return out
+
+        def source(v, what, kinds):
+            """(kind, theta column, constant) of a float or (kind, j)"""
+            if isinstance(v, (tuple, list)):
+                if len(v) != 2 or v[0] not in kinds or int(v[1]) != v[1] \
+                        or not 0 <= v[1] < 32:
+                    raise ValueError(f"{what}: expected a float or one of "
+                                     f"{kinds} with a theta column, got {v!r}")
+                return kinds.index(v[0]) + 1, int(v[1]), 0.0
+            if not np.isfinite(float(v)):
+                raise ValueError(f"{what}: {v!r} is not finite")
+            return 0, -1, float(v)
+
+        reactions = list(reactions)
+        R = len(reactions)
+        if not 1 <= R <= OdeTable.MAX_REACTIONS:
+            raise ValueError(f"1 to {OdeTable.MAX_REACTIONS} reactions, got {R}")
+        self.reactant_slots, self.net, self.rates = [], [], []
+        for r, (lhs, rhs, rate) in enumerate(reactions):
+            a, b = counts(lhs), counts(rhs)
+            if a.sum() > 2:
+                raise ValueError(f"reaction {r}: reactant order {a.sum()} > 2")
+            slots = [i for i in range(n) for _ in range(a[i])]
+            self.reactant_slots.append(tuple(slots + [-1] * (2 - len(slots))))
+            self.net.append([(i, int(c)) for i, c in enumerate(b - a) if c])
+            self.rates.append(source(rate, f"rate of reaction {r}",
+                                     ("theta", "log10theta")))
+        if isinstance(x_init, dict):
+            for k in x_init:
+                sp(k)
+            x_init = [x_init.get(s, 0.0) for s in self.species]
+        if len(x_init) != n:
+            raise ValueError(f"x_init has {len(x_init)} entries for {n} species")
+        self.x_init = [source(v, f"x_init of {s}", ("theta",))
+                       for s, v in zip(self.species, x_init)]
+        self.t_obs = np.atleast_1d(np.asarray(t_obs, dtype=np.float64))
+        T = self.t_obs.size
+        if self.t_obs.ndim != 1 or T < 1 or not np.all(np.isfinite(self.t_obs)) \
+                or self.t_obs[0] <= 0 or np.any(np.diff(self.t_obs) <= 0):
+            raise ValueError("t_obs must be positive and strictly increasing")
+        self.observed_species = tuple(self.species if observed is None
+                                      else observed)
+        obs = [sp(s) for s in self.observed_species]
+        if not obs or len(set(obs)) != len(obs):
+            raise ValueError("observed must name distinct species")
+        self.S = T * len(obs)
+        if self.S > OdeTable.MAX_STATS:
+            raise ValueError(f"S = T * len(observed) = {self.S} > "
+                             f"{OdeTable.MAX_STATS}")
+        if not (rtol > 0 and atol >= 0 and max_steps >= 1):
+            raise ValueError("rtol > 0, atol >= 0 and max_steps >= 1")
+        self.sigma, self.rtol, self.atol = float(sigma), float(rtol), float(atol)
+        self.max_steps = int(max_steps)
+        self.keys = tuple(keys) if keys is not None else tuple(
+            f"{s}_{j:03d}" for s in self.observed_species for j in range(T))
+        if len(self.keys) != self.S:
+            raise ValueError(f"{len(self.keys)} keys for {self.S} statistics")
+        self.name = name
+        self._x0 = x0
+        # theta columns the network reads: theta must have more than this
+        self.max_col = max(c for _, c, _ in self.rates + self.x_init)
+
+        tab = self.table = OdeTable()
+        tab.n_species, tab.n_reactions = n, R
+        tab.n_times, tab.n_observed = T, len(obs)
+        p = 0
+        for r in range(R):
+            tab.rate_kind[r], tab.rate_col[r], tab.rate_const[r] = self.rates[r]
+            tab.reactant[r][0], tab.reactant[r][1] = self.reactant_slots[r]
+            tab.pair_start[r] = p
+            for i, c in self.net[r]:
+                tab.pair[p] = (c << 8) | i
+                p += 1
+        tab.pair_start[R] = p
+        for i, (_, col, const) in enumerate(self.x_init):
+            tab.x_init_col[i], tab.x_init[i] = col, const
+        for o, i in enumerate(obs):
+            tab.observed[o] = i
+        tab.t_obs[:T] = self.t_obs.tolist()
+
+    def _check_theta(self, d):
+        if not self.max_col < d <= 32:
+            raise ValueError(f"the network reads theta column {self.max_col}; "
+                             f"theta has {d} columns (at most 32)")
+
+    def simulate(self, theta, seed, sid, offset):
+        self._check_theta(theta.shape[1])
+        return K.sim_mass_action_ode(theta, self.table, self.rtol, self.atol,
+                                     self.max_steps, self.sigma, seed, sid,
+                                     offset)
+
+    def simulate_host(self, theta, rng=None):
+        """scipy statement of the same model (for CPU baselines): RK45 at the
+        model's tolerances, [B, S]; noise needs ``rng`` when sigma > 0."""
+        from scipy.integrate import solve_ivp
+        theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
+        self._check_theta(theta.shape[1])
+        n, R = len(self.species), len(self.rates)
+        nu = np.zeros((n, R))
+        for r, pairs in enumerate(self.net):
+            for i, c in pairs:
+                nu[i, r] = c
+        slots = np.array(self.reactant_slots)
+        obs = [self.species.index(s) for s in self.observed_species]
+        out = np.empty((theta.shape[0], self.S))
+        for b, th in enumerate(theta):
+            k = np.array([c if kind == 0 else th[col] if kind == 1
+                          else 10.0 ** th[col] for kind, col, c in self.rates])
+            x0 = np.array([c if kind == 0 else th[col]
+                           for kind, col, c in self.x_init])
+
+            def f(t, x):
+                xe = np.append(x, 1.0)      # slot -1 reads the trailing 1
+                return nu @ (k * xe[slots[:, 0]] * xe[slots[:, 1]])
+            sol = solve_ivp(f, (0.0, self.t_obs[-1]), x0, method="RK45",
+                            t_eval=self.t_obs, rtol=self.rtol, atol=self.atol)
+            out[b] = sol.y[obs].ravel() if sol.success else np.inf
+        if self.sigma > 0:
+            out = out + self.sigma * rng.normal(size=out.shape)
+        return out
+
+    def observed(self):
+        x0 = self._x0
+        return x0 if isinstance(x0, dict) or x0 is None else dict(
+            zip(self.keys, x0))
 
 
 def _per_particle_accept(model, t, pars, sum_stats_calculator,

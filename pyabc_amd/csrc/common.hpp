@@ -108,6 +108,7 @@ int preload_select();
 int preload_stochastic();
 int preload_stochastic_full();
 int preload_stochastic_count();
+int preload_sim_ode();
 int preload_local();
 int preload_local_pdf32();
 int preload_sort();

@@ -810,6 +810,25 @@ def sim_gaussian_mean(theta, sigma, seed, sid, offset, out=None, B=None):
     return out
 
 
+def sim_mass_action_ode(theta, table, rtol, atol, max_steps, sigma, seed, sid,
+                        offset, out_T=None, B=None, steps_out=None):
+    """Mass-action ODE statistics of the rows of ``theta`` ([B, d]) for the
+    network ``table`` (a host ``_native.OdeTable``), stat-major [S, B]: row
+    ``o * n_times + j`` is observed species o at time j.  A proposal whose
+    integration fails is a column of +inf.  ``steps_out`` (int64 [B]) receives
+    the attempted steps per proposal."""
+    theta = _contig(theta, F64)
+    B = theta.shape[0] if B is None else B
+    S = table.n_times * table.n_observed
+    if out_T is None:
+        out_T = torch.empty((S, max(B, 1)), dtype=F64, device=_dev())
+    call("abc_sim_mass_action_ode_f64", ctypes.byref(table), ptr(theta), B,
+         theta.shape[1], float(rtol), float(atol), int(max_steps),
+         float(sigma), seed, sid, offset, ptr(out_T), out_T.shape[1],
+         ptr(steps_out), nat.stream())
+    return out_T
+
+
 # ---------------------------------------------------------------------------
 # exact inference (SURVEY 8(f) rank 3): stochastic kernels and acceptance
 # ---------------------------------------------------------------------------

@@ -163,6 +163,44 @@ def bench_count_kernel(B=1 << 20, calls=10):
             del stats
 
 
+def bench_sim_ode(B=1 << 20, calls=40, host_rows=512):
+    """abc_sim_mass_action_ode_f64 on the conversion reaction A <-> B
+    (log10 k uniform in [-1, 0.5], ten observation times up to t = 30, the
+    model's default tolerances): `calls` launches between two events, best
+    of 5; the right-hand-side evaluations are 2 + 6 attempted steps per
+    proposal, from the kernel's own step counts.  The CPU figure beside it is
+    simulate_host (scipy RK45, one thread) on the first `host_rows` rows."""
+    import time
+    from pyabc_amd.batch_models import MassActionODEModel
+    model = MassActionODEModel(
+        ["A", "B"], [({"A": 1}, {"B": 1}, ("log10theta", 0)),
+                     ({"B": 1}, {"A": 1}, ("log10theta", 1))],
+        [1.0, 0.0], np.linspace(3, 30, 10))
+    g = torch.Generator(device="cuda").manual_seed(6)
+    theta = torch.rand((B, 2), dtype=F64, device="cuda", generator=g) * 1.5 - 1
+    steps = torch.empty(B, dtype=torch.int64, device="cuda")
+    out = K.sim_mass_action_ode(theta, model.table, model.rtol, model.atol,
+                                model.max_steps, 0.0, 1, 3, 0, steps_out=steps)
+    rhs = 2 * B + 6 * int(steps.sum())
+
+    def run():
+        for _ in range(calls):
+            K.sim_mass_action_ode(theta, model.table, model.rtol, model.atol,
+                                  model.max_steps, 0.0, 1, 3, 0, out_T=out)
+    t = timed(run) / calls
+    th = theta[:host_rows].cpu().numpy()
+    t0 = time.perf_counter()
+    model.simulate_host(th)
+    t_host = (time.perf_counter() - t0) / host_rows
+    print(json.dumps({
+        "kernel": "sim_mass_action_ode_f64", "network": "conv", "ms": t * 1e3,
+        "units": B, "unit": "proposals", "units_per_s": B / t,
+        "rhs_evals_per_s": rhs / t, "mean_steps": float(steps.sum()) / B,
+        "max_steps": int(steps.max()), "failed": int(torch.isinf(out[0]).sum()),
+        "host_proposals_per_s": 1 / t_host, "host_rows": host_rows}),
+        flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -173,8 +211,13 @@ def main():
                          "single-fit equivalent")
     ap.add_argument("--count-kernel", action="store_true",
                     help="only the count-data kernels' rows")
+    ap.add_argument("--sim-ode", action="store_true",
+                    help="only the mass-action ODE model's row")
     args = ap.parse_args()
     torch.cuda.set_device(0)
+    if args.sim_ode:
+        bench_sim_ode()
+        return
     if args.normal_kernel:
         bench_normal_kernel()
         return
@@ -273,6 +316,8 @@ def main():
                                        acc_out=acc, guard_out=guard))
     report("pnorm_distance_f64", t, B, "particles", 8 * S + 10, "hbm",
            {"S": S})
+
+    bench_sim_ode()
 
     # ------- (f3) exact inference: kernel density + stochastic acceptance --
     var = torch.full((S,), 0.25, dtype=F64, device="cuda")
