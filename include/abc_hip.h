@@ -562,6 +562,109 @@ int abc_sim_mass_action_ode_f64(const abc_ode_table* table, const double* theta,
                                 int64_t ld, int64_t* steps_out,
                                 hipStream_t stream);
 
+/* ---------------- priors beyond the uniform box ---------------------------
+ * Replaces Distribution.pdf / Distribution.rvs          random_variables.py:425-452
+ * for a product of scipy.stats marginals.  The prior is this fixed-size
+ * marginal table, one entry per parameter in sorted-name order.  It is HOST
+ * memory: a call copies what it needs into the kernel's arguments.  Every
+ * transcendental constant is evaluated by the host, once, in fp64.
+ *
+ * Density.  With z = (theta - loc) / scale (a true division), the marginal's
+ * log density inside its support is
+ *   c + a log z + b log1p(-z) - e z - f z^2 - g |z| - k (log z)^2
+ * and mask says which terms exist (a term whose bit is clear is skipped, not
+ * multiplied by zero) and which ends of [zlo, zhi] belong to the support --
+ * the ends at which scipy's pdf is > 0.  c holds -log(scale).
+ *   family        c (+ -log scale)              terms             support
+ *   uniform       0                             -                 [0, 1]
+ *   norm          -log(2 pi)/2                  f = 1/2           (-inf, inf)
+ *   lognorm(s)    -log s - log(2 pi)/2          a = -1, k = 1/(2 s^2)  (0, inf)
+ *   expon         0                             e = 1             [0, inf)
+ *   laplace       -log 2                        g = 1             (-inf, inf)
+ *   loguniform    -log log(hi/lo)               a = -1            [lo, hi]
+ *   truncnorm     -log(2 pi)/2 - log(Phi(hi) - Phi(lo))   f = 1/2 [lo, hi]
+ *   gamma(s)      -lgamma(s)                    a = s - 1, e = 1  [0, inf), 0 out for s > 1
+ *   beta(s, t)    -betaln(s, t)                 a = s - 1, b = t - 1   [0, 1], an end out
+ *                                                                   for a shape > 1
+ * Draws.  family selects the transform of the uniform u; p0 .. p2 are its
+ * host constants: lognorm p0 = s; loguniform p0 = log lo, p1 = log hi - log lo;
+ * truncnorm p0 = Phi(lo), p1 = Phi(-hi), p2 = Phi(hi) - Phi(lo);
+ * gamma p0 = s; beta p0 = s, p1 = t. */
+#define ABC_PRIOR_MAX_DIM 32
+#define ABC_PRIOR_UNIFORM 0
+#define ABC_PRIOR_NORM 1
+#define ABC_PRIOR_LOGNORM 2
+#define ABC_PRIOR_EXPON 3
+#define ABC_PRIOR_LAPLACE 4
+#define ABC_PRIOR_LOGUNIFORM 5
+#define ABC_PRIOR_TRUNCNORM 6
+#define ABC_PRIOR_GAMMA 7
+#define ABC_PRIOR_BETA 8
+#define ABC_PRIOR_TERM_LOGZ 1    /* a log z */
+#define ABC_PRIOR_TERM_LOG1M 2   /* b log1p(-z) */
+#define ABC_PRIOR_TERM_LIN 4     /* e z */
+#define ABC_PRIOR_TERM_SQ 8      /* f z^2 */
+#define ABC_PRIOR_TERM_ABS 16    /* g |z| */
+#define ABC_PRIOR_TERM_LOGSQ 32  /* k (log z)^2 */
+#define ABC_PRIOR_LO_CLOSED 64   /* z == zlo is in the support */
+#define ABC_PRIOR_HI_CLOSED 128  /* z == zhi is in the support */
+/* tries of one gamma variate's Marsaglia-Tsang rejection (each accepts with
+ * probability > 0.95: all fail with probability < 2^-133), and the Philox
+ * blocks one table entry owns in stream sid + 1: two gamma variates (beta),
+ * each its tries and then one block for the shape < 1 boost */
+#define ABC_PRIOR_GAMMA_TRIES 31
+#define ABC_PRIOR_DRAW_BLOCKS 64
+typedef struct abc_prior_table {
+  double loc[ABC_PRIOR_MAX_DIM];
+  double scale[ABC_PRIOR_MAX_DIM]; /* finite, > 0 */
+  double zlo[ABC_PRIOR_MAX_DIM];
+  double zhi[ABC_PRIOR_MAX_DIM];
+  double c[ABC_PRIOR_MAX_DIM];
+  double a[ABC_PRIOR_MAX_DIM];
+  double b[ABC_PRIOR_MAX_DIM];
+  double e[ABC_PRIOR_MAX_DIM];
+  double f[ABC_PRIOR_MAX_DIM];
+  double g[ABC_PRIOR_MAX_DIM];
+  double k[ABC_PRIOR_MAX_DIM];
+  int32_t mask[ABC_PRIOR_MAX_DIM];
+  double p0[ABC_PRIOR_MAX_DIM];
+  double p1[ABC_PRIOR_MAX_DIM];
+  double p2[ABC_PRIOR_MAX_DIM];
+  int32_t family[ABC_PRIOR_MAX_DIM];
+} abc_prior_table;
+/* theta [B][d] row-major, 1 <= d <= 32.  Each output may be NULL:
+ *   logp[b]       = sum over the d marginals of the log density; -inf for a
+ *                   row outside the support (never NaN)
+ *   pd[b]         = exp(logp[b])
+ *   in_support[b] = 1 where the reference's prior.pdf(theta) > 0 (+inf counts):
+ *                   every z finite and inside its interval, and pd > 0;
+ *                   0 for a row holding a NaN
+ * Error of logp inside the support <= 1e-12 (1 + sum |terms| + sum |c|)
+ * ("Prior table").  A row's outputs depend on that row only. */
+int abc_prior_logpdf_f64(const double* theta, const abc_prior_table* table,
+                         int d, int64_t B, double* logp, double* pd,
+                         uint8_t* in_support, hipStream_t stream);
+/* theta[b][k] for b < B: the draw of marginal k from the uniform u at index
+ * (offset + b) d + k of raw Philox stream sid -- the number
+ * abc_prior_uniform_f64 takes, so a row depends on its global id offset + b
+ * only.  uniform: loc + scale u (bit-identical to abc_prior_uniform_f64);
+ * the other inversion families take max(u, 2^-54), so no draw is infinite:
+ *   norm ndtri(u); lognorm exp(s ndtri u); expon -log1p(-u);
+ *   laplace u > 1/2 ? -log(2 (1 - u)) : log(2 u);
+ *   loguniform exp(log lo + u (log hi - log lo));
+ *   truncnorm with v = Phi(lo) + u M, M = Phi(hi) - Phi(lo):
+ *     v <= 1/2 ? ndtri(v) : -ndtri(Phi(-hi) + (1 - u) M)   (no cancellation)
+ * gamma and beta (X / (X + Y) of two gammas) by Marsaglia-Tsang rejection
+ * with the U^(1/shape) boost below shape 1.  Entry i = (offset + b) d + k
+ * owns blocks 64 i .. 64 i + 63 of stream sid + 1: variate j in {0, 1} tries
+ * blocks 64 i + 32 j + t, t < 31 (normal = ndtri of words 0-1, acceptance
+ * uniform words 2-3), its boost uniform is words 0-1 of block 64 i + 32 j + 31.
+ * A variate whose 31 tries all fail is NaN (probability < 2^-133), which the
+ * support test rejects.                         random_variables.py:434 */
+int abc_prior_rvs_f64(const abc_prior_table* table, int d, uint64_t seed,
+                      uint64_t sid, uint64_t offset, int64_t B, double* theta,
+                      hipStream_t stream);
+
 /* ---------------- (f3) exact inference: stochastic acceptance -------------
  * SURVEY 8(f) rank 3.  Replaces, per evaluation b (stat-major stats_T):
  *   IndependentNormalKernel.__call__  (kind 0, prm = var)  distance/kernel.py:256-282

@@ -243,6 +243,11 @@ _SIGS = {
                                             c_dbl, c_i64, c_dbl, c_u64, c_u64,
                                             c_u64, c_ptr, c_i64, c_ptr,
                                             c_ptr]),
+    # the second / first argument is a HOST pointer to a PriorTable
+    "abc_prior_logpdf_f64": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr,
+                                     c_ptr, c_ptr]),
+    "abc_prior_rvs_f64": (c_int, [c_ptr, c_int, c_u64, c_u64, c_u64, c_i64,
+                                  c_ptr, c_ptr]),
 }
 
 
@@ -260,6 +265,26 @@ class OdeTable(ctypes.Structure):
         ("x_init", c_dbl * 8), ("x_init_col", ctypes.c_int32 * 8),
         ("observed", ctypes.c_int32 * 8), ("t_obs", c_dbl * 256),
     ]
+
+
+class PriorTable(ctypes.Structure):
+    """``abc_prior_table`` of include/abc_hip.h (the layout, the families
+    and the term mask are documented there): the marginals of a prior, built
+    by ``Distribution.device_table``."""
+    MAX_DIM = 32
+    (UNIFORM, NORM, LOGNORM, EXPON, LAPLACE, LOGUNIFORM, TRUNCNORM, GAMMA,
+     BETA) = range(9)
+    LOGZ, LOG1M, LIN, SQ, ABS, LOGSQ, LO_CLOSED, HI_CLOSED = (
+        1, 2, 4, 8, 16, 32, 64, 128)
+    _fields_ = [(n, c_dbl * 32) for n in (
+        "loc", "scale", "zlo", "zhi", "c", "a", "b", "e", "f", "g", "k")] + [
+        ("mask", ctypes.c_int32 * 32)] + [
+        (n, c_dbl * 32) for n in ("p0", "p1", "p2")] + [
+        ("family", ctypes.c_int32 * 32)]
+
+    def key(self):
+        """The table's bytes (hashable: two equal priors share an engine)."""
+        return bytes(self)
 
 
 _lib = None

@@ -54,7 +54,8 @@ int abc_preload(void) {
          abc::preload_distance() + abc::preload_select() + abc::preload_stochastic() +
          abc::preload_stochastic_full() + abc::preload_stochastic_count() +
          abc::preload_local() + abc::preload_local_pdf32() + abc::preload_local_mfma() +
-         abc::preload_local_mfma16() + abc::preload_sort() + abc::preload_sim_ode();
+         abc::preload_local_mfma16() + abc::preload_sort() + abc::preload_sim_ode() +
+         abc::preload_prior();
 }
 int abc_version(void) { return 10000; }  // 0.1.0
 }

@@ -109,6 +109,7 @@ int preload_stochastic();
 int preload_stochastic_full();
 int preload_stochastic_count();
 int preload_sim_ode();
+int preload_prior();
 int preload_local();
 int preload_local_pdf32();
 int preload_sort();

@@ -582,15 +582,29 @@ class GenerationEngine:
 
     def __init__(self, model, prior_lo, prior_scale, distance_p=2.0,
                  comm=None, seed=0, min_batch=1 << 16, max_batch=1 << 22,
-                 kde_precision="mfma", record_stats=False):
+                 kde_precision="mfma", record_stats=False, prior_table=None):
+        """The prior is a uniform box (``prior_lo``, ``prior_scale``: drawn
+        by abc_prior_uniform_f64, tested inside the proposal kernels, one
+        scalar density) or, with ``prior_table`` = (names,
+        ``_native.PriorTable``) from ``Distribution.device_table`` and no
+        box, any product of the table's families: drawn by
+        abc_prior_rvs_f64, proposals flagged and accepted rows weighted by
+        abc_prior_logpdf_f64."""
         self.model = model
         self.dev = torch.device("cuda", torch.cuda.current_device())
-        self.lo = torch.as_tensor(np.asarray(prior_lo, dtype=np.float64),
-                                  device=self.dev)
-        self.scale = torch.as_tensor(np.asarray(prior_scale, dtype=np.float64),
-                                     device=self.dev)
-        self.d = self.lo.numel()
-        self.prior_pd = float(np.prod(1.0 / np.asarray(prior_scale)))
+        if prior_table is None:
+            self.prior_table = None
+            self.lo = torch.as_tensor(np.asarray(prior_lo, dtype=np.float64),
+                                      device=self.dev)
+            self.scale = torch.as_tensor(
+                np.asarray(prior_scale, dtype=np.float64), device=self.dev)
+            self.d = self.lo.numel()
+            self.prior_pd = float(np.prod(1.0 / np.asarray(prior_scale)))
+        else:
+            names, self.prior_table = prior_table
+            self.lo = self.scale = None   # proposals carry no box test
+            self.d = len(names)
+            self.prior_pd = None          # per row, from the table
         self.p = distance_p
         self.comm = comm or Comm.single()
         self.seed = int(seed)
@@ -646,6 +660,15 @@ class GenerationEngine:
         """[lo, hi) of this rank's rows."""
         return self.row_ranges(n)[self.comm.rank]
 
+    def draw_prior(self, sid, offset, B):
+        """Prior rows with global ids offset .. offset + B - 1 (raw Philox
+        stream ``sid``; the table's gamma / beta marginals also read
+        ``sid + 1``, which no other purpose uses: _stream() ids are even)."""
+        if self.prior_table is None:
+            return K.prior_uniform(self.lo, self.scale, self.seed, sid,
+                                   offset, B)
+        return K.prior_rvs(self.prior_table, self.d, self.seed, sid, offset, B)
+
     # ------------------------------------------------------------------
     def sample_prior(self, t, n):
         """t = 0 / calibration: theta ~ prior, all accepted
@@ -653,8 +676,7 @@ class GenerationEngine:
         rows row_range(n); all-gathering in rank order gives the population
         a single GPU would draw."""
         lo, hi = self.row_range(n)
-        theta = K.prior_uniform(self.lo, self.scale, self.seed,
-                                self._stream(t, 0), lo, hi - lo)
+        theta = self.draw_prior(self._stream(t, 0), lo, hi - lo)
         stats = self.model.simulate(theta, self.seed, self._stream(t, 1), lo)
         return GenerationResult(theta=theta, stats_T=stats, n_eval=hi - lo,
                                 rec_stats_T=stats, n_rec=hi - lo)
@@ -721,8 +743,7 @@ class GenerationEngine:
             B = -(-B_glob // R)
             my_raw = raw_off + r * B
             if fit is None:
-                theta = K.prior_uniform(self.lo, self.scale, self.seed,
-                                        self._stream(t, stream_base), my_raw,
+                theta = self.draw_prior(self._stream(t, stream_base), my_raw,
                                         B)
                 nvs = [B] * R
             else:
@@ -731,6 +752,10 @@ class GenerationEngine:
                     self._sid(t, stream_base), my_raw, B)
                 if hasattr(fit, "start_pack"):
                     fit.start_pack()   # a deferred pack: after the proposals
+                if self.prior_table is not None:
+                    # the proposals came without a box test: prior.pdf > 0
+                    sup = K.prior_logpdf(theta_all, self.prior_table, B,
+                                         logp=False, pd=False)[2]
                 vpos, vcount = K.compact(sup)
                 nvs = comm.all_gather_ints(vcount)                  # sync 1
                 nv = nvs[r]
@@ -941,7 +966,16 @@ class GenerationEngine:
                 lp = fit.logpdf(mine)
             logpd = comm.all_gather_rows(
                 lp, [b - a for a, b in self.row_ranges(theta_acc.shape[0])])
-            if stochastic:
+            if self.prior_table is not None:
+                # per-row prior density of the population (every rank holds
+                # all of it: the same bits without a collective)
+                pd = K.prior_logpdf(theta_acc, self.prior_table, logp=False,
+                                    support=False)[1]
+                if stochastic:
+                    w = K.importance_weights_scaled(logpd, accw_acc * pd)
+                else:
+                    w = K.importance_weights(logpd, pd)
+            elif stochastic:
                 w = K.importance_weights_scaled(logpd, accw_acc, self.prior_pd)
             else:
                 w = K.importance_weights(logpd, None, self.prior_pd)

@@ -160,6 +160,32 @@ def prior_uniform(lo, scale, seed, sid, offset, B):
     return theta
 
 
+def prior_rvs(table, d, seed, sid, offset, B):
+    """Rows offset .. offset + B - 1 of the prior ``table`` (a host
+    ``_native.PriorTable`` of d marginals) -> [B, d]; row b is a function of
+    its global id offset + b (uniform u at index (offset + b) d + k of raw
+    stream ``sid``; gamma / beta also read raw stream ``sid + 1``)."""
+    theta = torch.empty((B, d), dtype=F64, device=_dev())
+    call("abc_prior_rvs_f64", ctypes.byref(table), d, seed, sid, offset, B,
+         ptr(theta), nat.stream())
+    return theta
+
+
+def prior_logpdf(theta, table, B=None, logp=True, pd=True, support=True):
+    """(logp, pd, in_support) of the rows of ``theta`` ([B, d]) under the
+    prior ``table``: the log density (-inf outside the support), its exp,
+    and the uint8 flag prior.pdf(theta) > 0.  An output not asked for is
+    None (and not computed)."""
+    theta = _contig(theta, F64)
+    B = theta.shape[0] if B is None else B
+    lp = torch.empty(B, dtype=F64, device=_dev()) if logp else None
+    p = torch.empty(B, dtype=F64, device=_dev()) if pd else None
+    sup = torch.empty(B, dtype=torch.uint8, device=_dev()) if support else None
+    call("abc_prior_logpdf_f64", ptr(theta), ctypes.byref(table),
+         theta.shape[1], B, ptr(lp), ptr(p), ptr(sup), nat.stream())
+    return lp, p, sup
+
+
 def compact(flags, out_idx=None, count=None):
     """Order-preserving positions of nonzero u8 flags; returns (idx,
     count_dev).  ``count``: an int64 device slot to write the count into

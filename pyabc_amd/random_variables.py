@@ -5,7 +5,10 @@ host-side configuration, evaluated per particle only on the per-particle
 (closure) sampling path.  The batch GPU path needs the prior's support test
 and density on the device: :meth:`Distribution.uniform_box` exposes a
 product of ``RV('uniform', loc, scale)`` marginals as (names, lo, scale)
-for the device kernels (prior support, random_variables.py:425-452).
+for the device kernels (prior support, random_variables.py:425-452), and
+:meth:`Distribution.device_table` describes a product of the nine families
+of :data:`DEVICE_FAMILIES` as the marginal table of the device's prior
+density and draws (``abc_prior_table``, include/abc_hip.h).
 """
 import numpy as np
 
@@ -84,8 +87,98 @@ class RV(RVBase):
         del names
         return float(loc), float(scale)
 
+    def device_marginal(self):
+        """This marginal as one entry of the device's prior table: a dict of
+        the ``abc_prior_table`` fields (include/abc_hip.h), every constant
+        evaluated here in fp64; None when the family is not one of
+        :data:`DEVICE_FAMILIES` or a scale or shape is not finite and
+        positive.  Shapes, loc and scale are read as scipy reads them
+        (positional or keyword)."""
+        from scipy import special as sc
+        from ._native import PriorTable as P
+        fam = DEVICE_FAMILIES.get(self.name)
+        frozen = self.distribution
+        if fam is None or not hasattr(frozen, "dist"):
+            return None
+        try:
+            shapes, loc, scale = frozen.dist._parse_args(*frozen.args,
+                                                         **frozen.kwds)
+            shapes = [float(s) for s in shapes]
+            loc, scale = float(loc), float(scale)
+        except (TypeError, ValueError):
+            return None
+        if not (np.isfinite(loc) and np.isfinite(scale) and scale > 0
+                and np.all(np.isfinite(shapes))):
+            return None
+        positive = fam not in (P.TRUNCNORM,)
+        if positive and not all(s > 0 for s in shapes):
+            return None
+        if fam in (P.LOGUNIFORM, P.TRUNCNORM) and not shapes[0] < shapes[1]:
+            return None
+        m = dict(loc=loc, scale=scale, c=-np.log(scale), family=fam, mask=0)
+        half_log_2pi = 0.5 * np.log(2 * np.pi)
+        if fam == P.NORM:
+            m.update(c=m["c"] - half_log_2pi, f=0.5, mask=P.SQ)
+        elif fam == P.LOGNORM:
+            s, = shapes
+            m.update(c=m["c"] - np.log(s) - half_log_2pi, a=-1.0,
+                     k=0.5 / (s * s), mask=P.LOGZ | P.LOGSQ, p0=s)
+        elif fam == P.EXPON:
+            m.update(e=1.0, mask=P.LIN)
+        elif fam == P.LAPLACE:
+            m.update(c=m["c"] - np.log(2.0), g=1.0, mask=P.ABS)
+        elif fam == P.LOGUNIFORM:
+            lo, hi = shapes
+            width = np.log(hi) - np.log(lo)
+            m.update(c=m["c"] - np.log(width), a=-1.0, mask=P.LOGZ,
+                     p0=np.log(lo), p1=width)
+        elif fam == P.TRUNCNORM:
+            lo, hi = shapes
+            # the mass Phi(hi) - Phi(lo) from the tail that holds it, so a
+            # small mass is never a difference of numbers near 1
+            if hi <= 0:
+                mass = sc.ndtr(hi) - sc.ndtr(lo)
+            elif lo >= 0:
+                mass = sc.ndtr(-lo) - sc.ndtr(-hi)
+            else:
+                mass = 1.0 - sc.ndtr(lo) - sc.ndtr(-hi)
+            if not mass > 0:
+                return None
+            m.update(c=m["c"] - half_log_2pi - np.log(mass), f=0.5,
+                     mask=P.SQ, p0=sc.ndtr(lo), p1=sc.ndtr(-hi), p2=mass)
+        elif fam == P.GAMMA:
+            s, = shapes
+            m.update(c=m["c"] - sc.gammaln(s), a=s - 1.0, e=1.0,
+                     mask=P.LIN | (P.LOGZ if s != 1 else 0), p0=s)
+        elif fam == P.BETA:
+            s, t = shapes
+            m.update(c=m["c"] - sc.betaln(s, t), a=s - 1.0, b=t - 1.0,
+                     mask=(P.LOGZ if s != 1 else 0)
+                     | (P.LOG1M if t != 1 else 0), p0=s, p1=t)
+        # the support in z, and which of its ends scipy gives a density > 0
+        zlo, zhi = (float(v) for v in frozen.dist.support(*shapes))
+        with np.errstate(all="ignore"):
+            if frozen.dist.pdf(zlo, *shapes) > 0:
+                m["mask"] |= P.LO_CLOSED
+            if frozen.dist.pdf(zhi, *shapes) > 0:
+                m["mask"] |= P.HI_CLOSED
+        m.update(zlo=zlo, zhi=zhi)
+        return m
+
     def __repr__(self):
         return f"<RV(name={self.name}, args={self.args} kwargs={self.kwargs})>"
+
+
+def _device_families():
+    from ._native import PriorTable as P
+    return {"uniform": P.UNIFORM, "norm": P.NORM, "lognorm": P.LOGNORM,
+            "expon": P.EXPON, "laplace": P.LAPLACE,
+            "loguniform": P.LOGUNIFORM, "reciprocal": P.LOGUNIFORM,
+            "truncnorm": P.TRUNCNORM, "gamma": P.GAMMA, "beta": P.BETA}
+
+
+# scipy.stats name -> family code of the device's prior table
+DEVICE_FAMILIES = _device_families()
 
 
 def _forward(method):
@@ -224,6 +317,24 @@ class Distribution(ParameterStructure):
             lo.append(b[0])
             sc.append(b[1])
         return names, np.array(lo), np.array(sc)
+
+    def device_table(self):
+        """(sorted names, ``_native.PriorTable``) when every marginal is a
+        plain :class:`RV` of one of :data:`DEVICE_FAMILIES` (not decorated,
+        not discrete) with finite positive scale and shapes; else None."""
+        from ._native import PriorTable
+        names = self.get_parameter_names()
+        if not 1 <= len(names) <= PriorTable.MAX_DIM:
+            return None
+        table = PriorTable()
+        for i, n in enumerate(names):
+            rv = self[n]
+            m = rv.device_marginal() if type(rv) is RV else None
+            if m is None:
+                return None
+            for field, v in m.items():
+                getattr(table, field)[i] = v
+        return names, table
 
 
 class ModelPerturbationKernel:

@@ -482,9 +482,15 @@ class ABCSMC:
 
     def _log_transition_pd(self, t, transitions, theta, parent=None):
         if t == 0:
-            # prior density: constant on the (uniform-box) support, where
-            # every recorded proposal lies (smc.py:737-749)
-            names = self.parameter_priors[0].uniform_box()[0]
+            # prior density (smc.py:737-749): per row from the device table,
+            # or constant on a uniform box's support, where every recorded
+            # proposal lies
+            prior = self.parameter_priors[0]
+            if prior.uniform_box() is None:
+                from . import kernels as K
+                return K.prior_logpdf(theta, prior.device_table()[1],
+                                      pd=False, support=False)[0]
+            names = prior.uniform_box()[0]
             par = Parameter(dict(zip(names, theta[0].cpu().numpy())))
             pd0 = self._create_prior_pdf()(0, par)
             return torch.full((theta.shape[0],), float(np.log(pd0)),

@@ -12,6 +12,7 @@ bytes / flops per unit of SURVEY.md 8(d) (DESIGN.md restates them):
     python tools/bench_kernels.py [--quick] > gpurun_out/kernels.jsonl
 """
 import argparse
+import ctypes
 import json
 import math
 import os
@@ -24,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from pyabc_amd import kernels as K  # noqa: E402
+from pyabc_amd._native import call as nat_call  # noqa: E402
 from pyabc_amd.engine import DeviceMVNFit  # noqa: E402
 
 HBM = 8.0e12
@@ -201,6 +203,77 @@ def bench_sim_ode(B=1 << 20, calls=40, host_rows=512):
         flush=True)
 
 
+def bench_prior(B=1 << 22, d=8, calls=20, reps=3):
+    """abc_prior_logpdf_f64 / abc_prior_rvs_f64 at B rows of d marginals for
+    an all-normal and an all-beta table (`calls` launches between two
+    events, best of 5), then config 1 of tools/bench_configs.py with a
+    normal prior beside the same config with its uniform prior, alternated
+    `reps` times in this process: the median generation (t >= 1) of each, and
+    the prior passes of one normal-prior generation (the support flags of a
+    round's proposals, the densities of the accepted rows) timed alone at
+    that config's shapes as a share of that generation."""
+    import contextlib
+    import io
+    import pyabc_amd as pa
+    from tools import bench_configs as bc
+    for name, rv in (("norm", pa.RV("norm", 1.0, 2.0)),
+                     ("beta", pa.RV("beta", 2.0, 5.0))):
+        table = pa.Distribution(
+            **{f"p{i}": rv for i in range(d)}).device_table()[1]
+        theta = K.prior_rvs(table, d, 1, 2, 0, B)
+        lp = torch.empty(B, dtype=F64, device="cuda")
+        pd = torch.empty(B, dtype=F64, device="cuda")
+        sup = torch.empty(B, dtype=torch.uint8, device="cuda")
+
+        def run_pdf():
+            for _ in range(calls):
+                nat_call("abc_prior_logpdf_f64", K.ptr(theta),
+                         ctypes.byref(table), d, B, K.ptr(lp), K.ptr(pd),
+                         K.ptr(sup), K.nat.stream())
+
+        def run_rvs():
+            for _ in range(calls):
+                nat_call("abc_prior_rvs_f64", ctypes.byref(table), d, 1, 2, 0,
+                         B, K.ptr(theta), K.nat.stream())
+        for kern, fn, nbytes in (("prior_logpdf_f64", run_pdf, 8 * d + 17),
+                                 ("prior_rvs_f64", run_rvs, 8 * d)):
+            t = timed(fn) / calls
+            print(json.dumps({"kernel": kern, "table": name, "B": B, "d": d,
+                              "ms": t * 1e3, "rows_per_s": B / t,
+                              "hbm_GB_per_s": B * nbytes / t / 1e9}),
+                  flush=True)
+
+    def c1(prior):
+        np.random.seed(0)
+        abc = pa.ABCSMC(pa.GaussianMeanModel(), prior, pa.PNormDistance(p=2),
+                        population_size=1000, eps=pa.MedianEpsilon(),
+                        sampler=pa.GPUBatchSampler(seed=1))
+        with contextlib.redirect_stdout(io.StringIO()):
+            out = bc.run("c1", abc, {"data": 2.5}, ["mean"], [2.5],
+                         minimum_epsilon=0.1, max_nr_populations=10)
+        assert out["all_batch"]
+        return out["generation_ms_median_t_ge_1"], abc.sampler.min_batch
+    priors = {"uniform": pa.Distribution(mean=pa.RV("uniform", 0, 5)),
+              "norm": pa.Distribution(mean=pa.RV("norm", 2.5, 1.5))}
+    ms = {k: [] for k in priors}
+    for _ in range(reps + 1):          # the first pass warms both up
+        for k, prior in priors.items():
+            g, min_batch = c1(prior)
+            ms[k].append(g)
+    table = priors["norm"].device_table()[1]
+    prop = K.prior_rvs(table, 1, 1, 2, 0, min_batch)
+    t_sup = timed(lambda: K.prior_logpdf(prop, table, logp=False, pd=False))
+    t_pd = timed(lambda: K.prior_logpdf(prop[:1000], table, logp=False,
+                                        support=False))
+    med = {k: float(np.median(v[1:])) for k, v in ms.items()}
+    print(json.dumps({
+        "config": "c1_quickstart_N1000", "generation_ms_uniform": med["uniform"],
+        "generation_ms_norm": med["norm"], "runs_ms": ms,
+        "prior_support_pass_ms": t_sup * 1e3, "prior_density_pass_ms": t_pd * 1e3,
+        "prior_share_of_generation": (t_sup + t_pd) * 1e3 / med["norm"]}),
+        flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -213,8 +286,14 @@ def main():
                     help="only the count-data kernels' rows")
     ap.add_argument("--sim-ode", action="store_true",
                     help="only the mass-action ODE model's row")
+    ap.add_argument("--prior", action="store_true",
+                    help="only the prior table's kernels and config 1 with a "
+                         "normal prior")
     args = ap.parse_args()
     torch.cuda.set_device(0)
+    if args.prior:
+        bench_prior()
+        return
     if args.sim_ode:
         bench_sim_ode()
         return
