@@ -32,8 +32,8 @@ extern "C" {
 const char* abc_last_error(void);
 int abc_version(void);
 /* Re-read the launch-shape tuning knobs (ABC_KDE_MFMA_SPLIT / _IB / _PIPE /
- * _LDS2 / _SMAJOR, ABC_KDE_TIER, ABC_LZ_IB / _TPB, ABC_KNN_ROWS) from the
- * environment.
+ * _LDS2 / _SMAJOR, ABC_KDE_TIER, ABC_LZ_IB / _TPB, ABC_KNN_ROWS,
+ * ABC_PROPOSE_GROUP, ABC_SSA_REFILL, ABC_SSA_GRID) from the environment.
  * The library reads them once, at the first launch that consults them; the
  * knobs only change how work maps to the chip, never a result bit
  * (tests/test_gpu_kernels.py knob tests).  No reference counterpart. */
@@ -664,6 +664,48 @@ int abc_prior_logpdf_f64(const double* theta, const abc_prior_table* table,
 int abc_prior_rvs_f64(const abc_prior_table* table, int d, uint64_t seed,
                       uint64_t sid, uint64_t offset, int64_t B, double* theta,
                       hipStream_t stream);
+
+/* ---------------- mass-action reaction-network SSA batch model -------------
+ * The stochastic model class of doc/examples/chemical_reaction.ipynb: the
+ * Markov jump process of the same network table (abc_ode_table, unchanged) on
+ * integer molecule counts, simulated exactly with Gillespie's direct method,
+ * one lane per proposal.  Per proposal with global id g = offset + b:
+ *   1. t = 0, j = 0, e = 0; k_r from the table as in the ODE model; a constant
+ *      x_init must be an integer in [0, 2^31), one from theta is rint(theta).
+ *   2. a_r = k_r * x_a * x_b in fp64, left to right; an empty slot contributes
+ *      1 and the second slot of "2A" contributes x_A - 1 (ordered pairs, whose
+ *      large-count limit is the ODE model's k A A).
+ *   3. a0 = a_0 + ... + a_(R-1), summed in this order afresh every event; every
+ *      add and multiply rounds on its own (no fma contraction).
+ *   4. a0 == 0: the state is frozen, every remaining observation takes the
+ *      current counts, done.
+ *   5. (w0..w3) = Philox block (g << 24) | e of stream (seed, sid), i.e.
+ *      uniforms 2i and 2i + 1 of abc_philox_uniform_f64 for i = (g << 24) | e:
+ *      u1 = u53(w0, w1), u2 = u53(w2, w3), tau = -log(1 - u1) / a0.
+ *   6. t_next = t + tau; while j < n_times and t_obs[j] < t_next, statistic
+ *      o * n_times + j takes the count of observed[o] and j advances; j ==
+ *      n_times: done.
+ *   7. Otherwise the first reaction whose running sum a_0 + ... + a_r exceeds
+ *      u2 * a0 fires (the last one with a_r > 0 if rounding leaves none): its
+ *      net stoichiometry is applied, t = t_next, e = e + 1.
+ * A proposal gets +inf in all of its S statistics when a rate is negative or
+ * not finite, an initial count from theta is negative, not finite or >= 2^31,
+ * a count would leave [0, 2^31), or e reaches max_events with an observation
+ * time still ahead.  No other proposal is affected and nothing is ever NaN.
+ * A proposal's column depends on (theta row, seed, sid, g) only, not on B, on
+ * its position or on how lanes are scheduled.  out_T is stat-major [S][ld],
+ * ld >= B; events_out (may be NULL) receives e per proposal; 1 <= max_events
+ * <= 2^24 and offset + B <= 2^40.  Two launch forms give the same bits:
+ * ABC_SSA_REFILL = 0 (default) one wave per 64 consecutive proposals, 1 a
+ * persistent grid (ABC_SSA_GRID waves; default 16 per compute unit) whose idle
+ * lanes claim the next proposals from a device counter.  The refill form keeps
+ * 64 such counters per device and hands them out in turn: at most 64 calls in
+ * flight per device. */
+int abc_sim_mass_action_ssa_f64(const abc_ode_table* table, const double* theta,
+                                int64_t B, int d, int64_t max_events,
+                                uint64_t seed, uint64_t sid, uint64_t offset,
+                                double* out_T, int64_t ld, int64_t* events_out,
+                                hipStream_t stream);
 
 /* ---------------- (f3) exact inference: stochastic acceptance -------------
  * SURVEY 8(f) rank 3.  Replaces, per evaluation b (stat-major stats_T):

@@ -43,7 +43,8 @@ from .temperature import (TemperatureBase, ListTemperature,  # noqa: E402
                           FrielPettittScheme, EssScheme)
 from .model import (Model, SimpleModel, ModelResult,  # noqa: E402
                     IntegratedModel, BatchModel, LinearGaussianModel,
-                    GaussianMeanModel, MassActionODEModel)
+                    GaussianMeanModel, MassActionODEModel,
+                    MassActionSSAModel)
 from .population import Particle, Population, ColumnarPopulation  # noqa: E402
 from .populationstrategy import (PopulationStrategy,  # noqa: E402
                                  ConstantPopulationSize, ListPopulationSize,

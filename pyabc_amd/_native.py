@@ -243,6 +243,9 @@ _SIGS = {
                                             c_dbl, c_i64, c_dbl, c_u64, c_u64,
                                             c_u64, c_ptr, c_i64, c_ptr,
                                             c_ptr]),
+    "abc_sim_mass_action_ssa_f64": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_i64,
+                                            c_u64, c_u64, c_u64, c_ptr, c_i64,
+                                            c_ptr, c_ptr]),
     # the second / first argument is a HOST pointer to a PriorTable
     "abc_prior_logpdf_f64": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr,
                                      c_ptr, c_ptr]),

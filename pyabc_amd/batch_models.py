@@ -7,7 +7,9 @@ The reference evaluates one Python model call per proposal
 models of BASELINE.json; each is one HIP kernel with
 Philox4x32-10 noise.  :class:`MassActionODEModel` is the model class of the
 reference's worked examples (doc/examples/conversion_reaction.ipynb,
-noise.ipynb): a reaction-network ODE integrated per proposal by one kernel.
+noise.ipynb): a reaction-network ODE integrated per proposal by one kernel;
+:class:`MassActionSSAModel` is the same network as a Markov jump process
+(doc/examples/chemical_reaction.ipynb), simulated exactly per proposal.
 """
 import numpy as np
 import torch
@@ -118,35 +120,12 @@ class GaussianMeanModel(BatchModel):
         return out.view(1, -1)
 
 
-class MassActionODEModel(BatchModel):
-    """Mass-action kinetics ``dx/dt = sum_r nu_r k_r prod(reactants of r)``
-    observed at fixed times, integrated on the device with an adaptive
-    Dormand-Prince 5(4) pair (scipy ``RK45``'s controller), one lane per
-    proposal.
+class _MassActionNetwork(BatchModel):
+    """What the mass-action models share: the network description, its
+    validation and its compiled ``OdeTable``."""
 
-    ``species``: 1 to 8 names.  ``reactions``: 1 to 16 entries ``(reactants,
-    products, rate)``; reactants and products are dicts ``name -> count``
-    (non-negative integers, at most two reactant molecules: ``{}``, ``{A: 1}``,
-    ``{A: 1, B: 1}``, ``{A: 2}``; the propensity of ``2A ->`` is ``k A A``);
-    ``rate`` is a float, ``("theta", j)`` (column j of theta) or
-    ``("log10theta", j)`` (``10 ** theta_j``).  ``x_init``: per species (a
-    sequence in species order, or a dict by name, missing names starting at
-    0) a float or ``("theta", j)``.
-    ``t_obs``: strictly increasing positive times; ``observed``: the observed
-    species (default all).
-
-    Statistics: species blocks in ``observed`` order, time-major within a
-    block -- statistic ``o * T + j`` is observed species o at ``t_obs[j]``,
-    default key ``f"{species}_{j:03d}"``; ``S = T * len(observed) <= 256``.
-    With ``sigma > 0`` the noise is :class:`LinearGaussianModel`'s (the same
-    Philox stream and fast normals).  A proposal whose integration needs more
-    than ``max_steps`` attempted steps or stops being finite has ``+inf`` in
-    every statistic, so it is rejected and never a NaN.
-    """
-
-    def __init__(self, species, reactions, x_init, t_obs, observed=None,
-                 sigma=0.0, rtol=1e-6, atol=1e-9, max_steps=100000, keys=None,
-                 name="mass_action_ode", x0=None):
+    def _init_network(self, species, reactions, x_init, t_obs, observed,
+                      keys, name, x0):
         from ._native import OdeTable
         self.species = tuple(species)
         n = len(self.species)
@@ -217,10 +196,6 @@ class MassActionODEModel(BatchModel):
         if self.S > OdeTable.MAX_STATS:
             raise ValueError(f"S = T * len(observed) = {self.S} > "
                              f"{OdeTable.MAX_STATS}")
-        if not (rtol > 0 and atol >= 0 and max_steps >= 1):
-            raise ValueError("rtol > 0, atol >= 0 and max_steps >= 1")
-        self.sigma, self.rtol, self.atol = float(sigma), float(rtol), float(atol)
-        self.max_steps = int(max_steps)
         self.keys = tuple(keys) if keys is not None else tuple(
             f"{s}_{j:03d}" for s in self.observed_species for j in range(T))
         if len(self.keys) != self.S:
@@ -252,6 +227,48 @@ class MassActionODEModel(BatchModel):
         if not self.max_col < d <= 32:
             raise ValueError(f"the network reads theta column {self.max_col}; "
                              f"theta has {d} columns (at most 32)")
+
+    def observed(self):
+        x0 = self._x0
+        return x0 if isinstance(x0, dict) or x0 is None else dict(
+            zip(self.keys, x0))
+
+
+class MassActionODEModel(_MassActionNetwork):
+    """Mass-action kinetics ``dx/dt = sum_r nu_r k_r prod(reactants of r)``
+    observed at fixed times, integrated on the device with an adaptive
+    Dormand-Prince 5(4) pair (scipy ``RK45``'s controller), one lane per
+    proposal.
+
+    ``species``: 1 to 8 names.  ``reactions``: 1 to 16 entries ``(reactants,
+    products, rate)``; reactants and products are dicts ``name -> count``
+    (non-negative integers, at most two reactant molecules: ``{}``, ``{A: 1}``,
+    ``{A: 1, B: 1}``, ``{A: 2}``; the propensity of ``2A ->`` is ``k A A``);
+    ``rate`` is a float, ``("theta", j)`` (column j of theta) or
+    ``("log10theta", j)`` (``10 ** theta_j``).  ``x_init``: per species (a
+    sequence in species order, or a dict by name, missing names starting at
+    0) a float or ``("theta", j)``.
+    ``t_obs``: strictly increasing positive times; ``observed``: the observed
+    species (default all).
+
+    Statistics: species blocks in ``observed`` order, time-major within a
+    block -- statistic ``o * T + j`` is observed species o at ``t_obs[j]``,
+    default key ``f"{species}_{j:03d}"``; ``S = T * len(observed) <= 256``.
+    With ``sigma > 0`` the noise is :class:`LinearGaussianModel`'s (the same
+    Philox stream and fast normals).  A proposal whose integration needs more
+    than ``max_steps`` attempted steps or stops being finite has ``+inf`` in
+    every statistic, so it is rejected and never a NaN.
+    """
+
+    def __init__(self, species, reactions, x_init, t_obs, observed=None,
+                 sigma=0.0, rtol=1e-6, atol=1e-9, max_steps=100000, keys=None,
+                 name="mass_action_ode", x0=None):
+        self._init_network(species, reactions, x_init, t_obs, observed, keys,
+                           name, x0)
+        if not (rtol > 0 and atol >= 0 and max_steps >= 1):
+            raise ValueError("rtol > 0, atol >= 0 and max_steps >= 1")
+        self.sigma, self.rtol, self.atol = float(sigma), float(rtol), float(atol)
+        self.max_steps = int(max_steps)
 
     def simulate(self, theta, seed, sid, offset):
         self._check_theta(theta.shape[1])
@@ -289,10 +306,116 @@ class MassActionODEModel(BatchModel):
             out = out + self.sigma * rng.normal(size=out.shape)
         return out
 
-    def observed(self):
-        x0 = self._x0
-        return x0 if isinstance(x0, dict) or x0 is None else dict(
-            zip(self.keys, x0))
+
+class MassActionSSAModel(_MassActionNetwork):
+    """The Markov jump process of a mass-action network on integer molecule
+    counts, observed at fixed times and simulated exactly on the device with
+    Gillespie's direct method, one lane per proposal (the model class of the
+    reference's doc/examples/chemical_reaction.ipynb).
+
+    The network description, the statistic layout ``o * T + j`` and the
+    default keys are :class:`MassActionODEModel`'s.  What differs: the state
+    is integer counts; a constant ``x_init`` entry must be a non-negative
+    integer and a ``("theta", j)`` one is ``rint(theta_j)``; the propensity of
+    ``2A ->`` is ``k x_A (x_A - 1)``, the ordered-pair convention, whose
+    large-count limit is the ODE model's ``k A A``; and there is no ``sigma``:
+    observation noise is what ``BinomialKernel`` / ``PoissonKernel`` /
+    ``NegativeBinomialKernel`` model.  include/abc_hip.h states the process
+    and its random-number stream; :meth:`simulate_host` restates it in numpy.
+
+    A proposal with a negative or non-finite rate, an initial count from
+    theta outside ``[0, 2^31)``, a count leaving that range, or more than
+    ``max_events`` (1 to 2^24) events before the last observation time has
+    ``+inf`` in every statistic: a p-norm distance rejects it, never a NaN.
+    ``kernels.count_kernel`` answers a ``+inf`` statistic as scipy's logpmf
+    does, with a NaN density, and its fused acceptance (``NaN >= u`` is
+    false) rejects the proposal.
+    """
+
+    def __init__(self, species, reactions, x_init, t_obs, observed=None,
+                 max_events=1 << 20, keys=None, name="mass_action_ssa",
+                 x0=None):
+        self._init_network(species, reactions, x_init, t_obs, observed, keys,
+                           name, x0)
+        for s, (kind, _, c) in zip(self.species, self.x_init):
+            if kind == 0 and not (0 <= c < 2 ** 31 and c == int(c)):
+                raise ValueError(f"x_init of {s}: a molecule count must be an "
+                                 f"integer in [0, 2^31), got {c!r}")
+        if int(max_events) != max_events or not 1 <= max_events <= 1 << 24:
+            raise ValueError("1 <= max_events <= 2^24")
+        self.max_events = int(max_events)
+
+    def simulate(self, theta, seed, sid, offset, events_out=None):
+        self._check_theta(theta.shape[1])
+        return K.sim_mass_action_ssa(theta, self.table, self.max_events, seed,
+                                     sid, offset, events_out=events_out)
+
+    def simulate_host(self, theta, u, info=False, tie_tol=1e-9):
+        """The same process in numpy on caller-supplied uniforms: ``u[b]``
+        holds ``(u1, u2)`` of event e of row b at ``[2 e, 2 e + 1]``.  The
+        propensities and their sums are fp64 in the device's order; event
+        times are carried in ``numpy.longdouble``.  Returns ``[B, S]``; with
+        ``info`` also the events fired per row and whether the row came
+        within a relative ``tie_tol`` of a tie (an event time against an
+        observation time, or ``u2 a0`` against a running sum), where one
+        rounding could change the path."""
+        theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
+        u = np.atleast_2d(np.asarray(u, dtype=np.float64))
+        self._check_theta(theta.shape[1])
+        T, obs = self.t_obs.size, [self.species.index(s)
+                                   for s in self.observed_species]
+        out = np.empty((theta.shape[0], self.S))
+        events = np.zeros(theta.shape[0], dtype=np.int64)
+        tie = np.zeros(theta.shape[0], dtype=bool)
+        for b, th in enumerate(theta):
+            k = np.array([c if kind == 0 else th[col] if kind == 1
+                          else 10.0 ** th[col] for kind, col, c in self.rates])
+            x = np.array([c if kind == 0 else np.rint(th[col])
+                          for kind, col, c in self.x_init])
+            stats = np.full((len(obs), T), np.inf)
+            ok = np.all((k >= 0) & (k < np.inf)) and \
+                np.all((x >= 0) & (x < 2.0 ** 31))
+            x = x.astype(np.int64) if ok else x
+            t, j, e = np.longdouble(0), 0, 0
+            while ok:
+                a = np.empty(len(k))
+                for r, (sa, sb) in enumerate(self.reactant_slots):
+                    v = k[r]
+                    if sa >= 0:
+                        v = v * np.float64(x[sa])
+                    if sb >= 0:
+                        v = v * np.float64(x[sb] - (sb == sa))
+                    a[r] = v
+                run = np.cumsum(a)      # sequential fp64 adds
+                a0 = run[-1]
+                if a0 == 0:
+                    stats[:, j:] = x[obs][:, None]
+                    break
+                if 2 * e + 1 >= u.shape[1]:
+                    raise ValueError(f"row {b} needs more than {e} events' "
+                                     f"uniforms")
+                u1, u2 = u[b, 2 * e], u[b, 2 * e + 1]
+                tn = t + np.longdouble(-np.log(1.0 - u1) / a0)
+                tie[b] |= bool(np.any(
+                    np.abs(self.t_obs[j:] - tn) <= tie_tol * self.t_obs[j:]))
+                while j < T and self.t_obs[j] < tn:
+                    stats[:, j] = x[obs]
+                    j += 1
+                if j == T:
+                    break
+                target = u2 * a0
+                tie[b] |= bool(np.any(np.abs(run[a > 0] - target)
+                                      <= tie_tol * a0))
+                hit = np.flatnonzero(run > target)
+                r = hit[0] if hit.size else np.flatnonzero(a > 0)[-1]
+                for i, c in self.net[r]:
+                    x[i] += c
+                t, e = tn, e + 1
+                if x.min() < 0 or x.max() >= 2 ** 31 or e >= self.max_events:
+                    stats[:] = np.inf
+                    break
+            out[b], events[b] = stats.ravel(), e
+        return (out, events, tie) if info else out
 
 
 def _per_particle_accept(model, t, pars, sum_stats_calculator,

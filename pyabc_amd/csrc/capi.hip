@@ -22,7 +22,8 @@ constexpr const char* kKnobNames[kKnobCount] = {
     "ABC_KDE_MFMA_SPLIT", "ABC_KDE_MFMA_IB",   "ABC_KDE_MFMA_PIPE",
     "ABC_KDE_MFMA_LDS2",  "ABC_KDE_MFMA_SMAJOR", "ABC_KDE_TIER",
     "ABC_LZ_IB",          "ABC_LZ_TPB",          "ABC_KNN_ROWS",
-    "ABC_KDE_PARENT_SHIFT", "ABC_KDE_PARENT_WIN", "ABC_PROPOSE_GROUP"};
+    "ABC_KDE_PARENT_SHIFT", "ABC_KDE_PARENT_WIN", "ABC_PROPOSE_GROUP",
+    "ABC_SSA_REFILL",     "ABC_SSA_GRID"};
 std::atomic<int> g_knobs[kKnobCount];
 std::once_flag g_knobs_once;
 
@@ -55,7 +56,7 @@ int abc_preload(void) {
          abc::preload_stochastic_full() + abc::preload_stochastic_count() +
          abc::preload_local() + abc::preload_local_pdf32() + abc::preload_local_mfma() +
          abc::preload_local_mfma16() + abc::preload_sort() + abc::preload_sim_ode() +
-         abc::preload_prior();
+         abc::preload_sim_ssa() + abc::preload_prior();
 }
 int abc_version(void) { return 10000; }  // 0.1.0
 }

@@ -47,6 +47,8 @@ enum Knob : int {
   kKnobKdeParentShift,    // ABC_KDE_PARENT_SHIFT
   kKnobKdeParentWin,      // ABC_KDE_PARENT_WIN
   kKnobProposeGroup,      // ABC_PROPOSE_GROUP (1 four lanes per proposal, 0 one)
+  kKnobSsaRefill,         // ABC_SSA_REFILL (1 persistent grid with lane refill, 0 plain)
+  kKnobSsaGrid,           // ABC_SSA_GRID (waves of the refill form's grid)
   kKnobCount
 };
 // the knob's integer value, or dflt when the variable is unset
@@ -109,6 +111,7 @@ int preload_stochastic();
 int preload_stochastic_full();
 int preload_stochastic_count();
 int preload_sim_ode();
+int preload_sim_ssa();
 int preload_prior();
 int preload_local();
 int preload_local_pdf32();

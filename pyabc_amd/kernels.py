@@ -337,7 +337,7 @@ def row_pad():
 
 def reload_tuning():
     """Re-read the launch-shape tuning knobs (ABC_KDE_MFMA_*, ABC_KDE_TIER,
-    ABC_LZ_*) from os.environ; the library reads them once per process
+    ABC_LZ_*, ABC_SSA_*) from os.environ; the library reads them once per process
     (abc_tuning_reload).  They never change a result bit."""
     nat.lib().abc_tuning_reload()
 
@@ -852,6 +852,24 @@ def sim_mass_action_ode(theta, table, rtol, atol, max_steps, sigma, seed, sid,
          theta.shape[1], float(rtol), float(atol), int(max_steps),
          float(sigma), seed, sid, offset, ptr(out_T), out_T.shape[1],
          ptr(steps_out), nat.stream())
+    return out_T
+
+
+def sim_mass_action_ssa(theta, table, max_events, seed, sid, offset,
+                        out_T=None, B=None, events_out=None):
+    """Gillespie direct-method statistics (integer counts as fp64) of the rows
+    of ``theta`` ([B, d]) for the network ``table`` (a host
+    ``_native.OdeTable``), stat-major [S, B]; the process is stated in
+    include/abc_hip.h.  A failed proposal is a column of +inf.
+    ``events_out`` (int64 [B]) receives the events fired per proposal."""
+    theta = _contig(theta, F64)
+    B = theta.shape[0] if B is None else B
+    S = table.n_times * table.n_observed
+    if out_T is None:
+        out_T = torch.empty((S, max(B, 1)), dtype=F64, device=_dev())
+    call("abc_sim_mass_action_ssa_f64", ctypes.byref(table), ptr(theta), B,
+         theta.shape[1], int(max_events), seed, sid, offset, ptr(out_T),
+         out_T.shape[1], ptr(events_out), nat.stream())
     return out_T
 
 

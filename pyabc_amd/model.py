@@ -5,11 +5,12 @@ reference; batch models (:mod:`pyabc_amd.batch_models`) are what the GPU
 sampler evaluates B proposals at a time on the device.
 """
 from .batch_models import (BatchModel, LinearGaussianModel,
-                           GaussianMeanModel, MassActionODEModel)
+                           GaussianMeanModel, MassActionODEModel,
+                           MassActionSSAModel)
 
 __all__ = ["ModelResult", "Model", "SimpleModel", "IntegratedModel",
            "BatchModel", "LinearGaussianModel", "GaussianMeanModel",
-           "MassActionODEModel"]
+           "MassActionODEModel", "MassActionSSAModel"]
 
 
 class ModelResult:

@@ -274,6 +274,84 @@ def bench_prior(B=1 << 22, d=8, calls=20, reps=3):
         flush=True)
 
 
+def bench_sim_ssa(B=1 << 20, calls=10, reps=7, host_rows=256):
+    """abc_sim_mass_action_ssa_f64 on pyABC's chemical-reaction model 1 (X + Y
+    -> 2Y from (40, 3), twenty observation times up to 0.1): a skewed batch
+    (log10 k uniform over [-0.5, 1.5]) and a homogeneous one (k = 2.3 in every
+    row), each in the plain form, the refill form at its default grid and at
+    8 and 32 waves per compute unit.  The forms alternate within one process;
+    a row reports the median of `reps` windows of `calls` launches and their
+    spread (max - min) / median, the figure a difference between two forms
+    has to exceed.  Events are the kernel's own counts.  The CPU figure is
+    simulate_host on the first `host_rows` rows of the skewed batch."""
+    import os
+    import time
+    from pyabc_amd.batch_models import MassActionSSAModel
+    model = MassActionSSAModel(
+        ["X", "Y"], [({"X": 1, "Y": 1}, {"Y": 2}, ("log10theta", 0))],
+        [40, 3], np.linspace(0.005, 0.1, 20))
+    g = torch.Generator(device="cuda").manual_seed(6)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    forms = {"plain": (0, None), "refill": (1, None),
+             "refill_8_per_cu": (1, 8 * cus), "refill_32_per_cu": (1, 32 * cus)}
+
+    def select(refill, grid):
+        os.environ["ABC_SSA_REFILL"] = str(refill)
+        os.environ.pop("ABC_SSA_GRID", None)
+        if grid:
+            os.environ["ABC_SSA_GRID"] = str(grid)
+        K.reload_tuning()
+
+    batches = {
+        "skewed": torch.rand((B, 1), dtype=F64, device="cuda", generator=g) * 2 - 0.5,
+        "homogeneous": torch.full((B, 1), float(np.log10(2.3)), dtype=F64,
+                                  device="cuda")}
+    for bname, theta in batches.items():
+        ev = torch.empty(B, dtype=torch.int64, device="cuda")
+        select(0, None)
+        want = K.sim_mass_action_ssa(theta, model.table, model.max_events, 1, 3,
+                                     0, events_out=ev)
+        events = int(ev.sum())
+        out = torch.empty_like(want)
+        ms = {f: [] for f in forms}
+        for rep in range(reps + 1):         # the first round warms up
+            for f, (refill, grid) in forms.items():
+                select(refill, grid)
+                e0 = torch.cuda.Event(enable_timing=True)
+                e1 = torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(calls):
+                    K.sim_mass_action_ssa(theta, model.table, model.max_events,
+                                          1, 3, 0, out_T=out)
+                e1.record()
+                torch.cuda.synchronize()
+                if rep:
+                    ms[f].append(e0.elapsed_time(e1) / calls)
+                else:
+                    assert torch.equal(out, want), f
+        for f, v in ms.items():
+            t = float(np.median(v)) * 1e-3
+            print(json.dumps({
+                "kernel": "sim_mass_action_ssa_f64", "network": "chem",
+                "batch": bname, "form": f, "ms": t * 1e3,
+                "spread": (max(v) - min(v)) / float(np.median(v)),
+                "units": B, "unit": "proposals", "units_per_s": B / t,
+                "events_per_s": events / t, "mean_events": events / B,
+                "max_events": int(ev.max())}), flush=True)
+    os.environ.pop("ABC_SSA_REFILL", None)
+    os.environ.pop("ABC_SSA_GRID", None)
+    K.reload_tuning()
+    th = batches["skewed"][:host_rows].cpu().numpy()
+    u = np.random.default_rng(0).uniform(size=(host_rows, 128))
+    t0 = time.perf_counter()
+    _, hev, _ = model.simulate_host(th, u, info=True)
+    t_host = time.perf_counter() - t0
+    print(json.dumps({"kernel": "simulate_host", "network": "chem",
+                      "host_proposals_per_s": host_rows / t_host,
+                      "host_events_per_s": int(hev.sum()) / t_host,
+                      "host_rows": host_rows}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -286,6 +364,9 @@ def main():
                     help="only the count-data kernels' rows")
     ap.add_argument("--sim-ode", action="store_true",
                     help="only the mass-action ODE model's row")
+    ap.add_argument("--sim-ssa", action="store_true",
+                    help="only the mass-action SSA model's rows: both launch "
+                         "forms on a skewed and a homogeneous batch")
     ap.add_argument("--prior", action="store_true",
                     help="only the prior table's kernels and config 1 with a "
                          "normal prior")
@@ -296,6 +377,9 @@ def main():
         return
     if args.sim_ode:
         bench_sim_ode()
+        return
+    if args.sim_ssa:
+        bench_sim_ssa()
         return
     if args.normal_kernel:
         bench_normal_kernel()
